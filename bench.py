@@ -12,6 +12,14 @@ Launch (driver contract):
       --master-addr 127.0.0.1 bench.py --gpus N ...      # DP over RCCL
 
 Rank 0 prints ONE JSON line with the whole-job aggregate tokens/sec.
+
+A plain run does only what that line needs: set up, warm up, time the
+steps, print. ``--dump-outputs DIR`` additionally writes what the last
+timed step computed (see ``dump_outputs``) so two builds can be compared
+output for output; the model init, the batch and the sample indices are
+all seeded, so the same arguments give the same inputs on every run.
+``--full`` is reserved for measurements beyond the headline figure; this
+benchmark has none today, so it changes nothing.
 """
 
 import argparse
@@ -20,6 +28,7 @@ import math
 import os
 import time
 
+import numpy as np
 import torch
 
 from progen_amd import ProGenBase, ProGenConfig
@@ -44,6 +53,26 @@ CONFIGS = {
 }
 
 
+DUMP_SAMPLE = 1 << 22  # parameter elements kept by --dump-outputs (16 MiB f32)
+
+
+def dump_outputs(out_dir, loss, flat_params):
+    """Write what a caller of the timed step receives after its last
+    call: the step's loss (``loss.npy``, shape (1,)) and the parameters it
+    updated (``params.npy``), both float32. A parameter buffer larger than
+    DUMP_SAMPLE elements is reduced to a fixed, seeded, sorted sample of
+    that many elements so the dump stays far below 64 MB."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"),
+            loss.detach().float().reshape(1).cpu().numpy())
+    flat = flat_params.detach()
+    if flat.numel() > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(1234).integers(
+            0, flat.numel(), size=DUMP_SAMPLE, dtype=np.int64))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    np.save(os.path.join(out_dir, "params.npy"), flat.float().cpu().numpy())
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -57,7 +86,17 @@ def main():
                         "GEMMs (fwd+dgrad; wgrad stays bf16) — the "
                         "BASELINE #5 fp8 mode; reported dtype becomes "
                         "bf16+fp8")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's loss "
+                        "and (a seeded sample of) the updated parameters "
+                        "to DIR/<name>.npy as float32")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline "
+                        "figure (none exist today; a plain run is already "
+                        "the whole benchmark)")
     args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
     if args.fp8:
         from progen_amd.ops import fp8 as _fp8
         _fp8.ENABLED = True
@@ -177,6 +216,9 @@ def main():
         print(f"[bench] WARNING: final loss is {final_loss} — the step "
               f"work is still representative but the trajectory is not",
               file=sys.stderr)
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_loss, optim.space.flat)
 
     # MAX over ranks
     if world > 1:

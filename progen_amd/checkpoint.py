@@ -16,7 +16,9 @@ params without torch).
 
 from __future__ import annotations
 
+import os
 import pickle
+import tempfile
 import time
 from functools import partial
 from pathlib import Path
@@ -108,7 +110,7 @@ def gcs_get_last_checkpoint(bucket) -> Optional[Dict]:
     if len(blobs) == 0:
         return None
     last = blobs[-1]
-    filename = f"/tmp/{last.name}"
+    filename = os.path.join(tempfile.gettempdir(), last.name)
     with open(filename, "wb") as f:
         last.download_to_file(f, timeout=GCS_READ_TIMEOUT)
     with open(filename, "rb") as f:
@@ -122,7 +124,7 @@ def gcs_save_checkpoint(bucket, package: Dict,
     num_checkpoints = len(blobs)
 
     filename = f"ckpt_{unix_time}.pkl"
-    tmp_path = f"/tmp/{filename}"
+    tmp_path = os.path.join(tempfile.gettempdir(), filename)
     with open(tmp_path, "wb") as f:
         pickle.dump(package, f)
     blob = bucket.blob(filename)

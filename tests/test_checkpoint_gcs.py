@@ -4,6 +4,8 @@ surface the code touches — the real client needs network + credentials,
 but the save/get-last/prune protocol is backend logic and is covered
 here (reference parity: checkpoint.py:41-81)."""
 
+import tempfile
+
 import torch
 
 from progen_amd import checkpoint as cp
@@ -43,7 +45,9 @@ def _pkg(i):
 
 
 def test_gcs_roundtrip_and_prune(monkeypatch, tmp_path):
-    # keep /tmp staging inside the test sandbox
+    # keep the staging files inside the test sandbox: a fixed name in the
+    # shared temp dir may already exist there, owned by another user
+    monkeypatch.setattr(tempfile, "tempdir", str(tmp_path))
     monkeypatch.setattr(cp.time, "time", lambda: 1_700_000_000 + len(b.store))
     b = FakeBucket()
 
