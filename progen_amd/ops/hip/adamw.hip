@@ -107,8 +107,8 @@ __global__ __launch_bounds__(ADAMW_BLOCK) void grad_sumsq_kernel(
 
 extern "C" {
 
-void grad_sumsq_launch(const void* grads, float* out, long long numel,
-                       bool is_bf16, hipStream_t stream) {
+hipError_t grad_sumsq_launch(const void* grads, float* out, long long numel,
+                             bool is_bf16, hipStream_t stream) {
   long long nv = numel / (is_bf16 ? 8 : 4);
   int grid = (int)((nv + ADAMW_BLOCK - 1) / ADAMW_BLOCK);
   if (grid > 2048) grid = 2048;
@@ -116,17 +116,20 @@ void grad_sumsq_launch(const void* grads, float* out, long long numel,
     grad_sumsq_kernel<true><<<grid, ADAMW_BLOCK, 0, stream>>>(grads, out, nv);
   else
     grad_sumsq_kernel<false><<<grid, ADAMW_BLOCK, 0, stream>>>(grads, out, nv);
+  return hipGetLastError();
 }
 
-void fused_adamw_launch(float* master, void* params, const void* grads,
-                        float* exp_avg, float* exp_avg_sq,
-                        const long long* starts, const long long* ends,
-                        const int* decay_flags, int nchunks, float lr,
-                        float b1, float b2, float eps, float wd,
-                        int* step_dev, float grad_scale,
-                        const float* clip_coef, bool is_bf16,
-                        long long shard_off, hipStream_t stream) {
+hipError_t fused_adamw_launch(float* master, void* params, const void* grads,
+                              float* exp_avg, float* exp_avg_sq,
+                              const long long* starts, const long long* ends,
+                              const int* decay_flags, int nchunks, float lr,
+                              float b1, float b2, float eps, float wd,
+                              int* step_dev, float grad_scale,
+                              const float* clip_coef, bool is_bf16,
+                              long long shard_off, hipStream_t stream) {
   step_inc_kernel<<<1, 1, 0, stream>>>(step_dev, clip_coef);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return err;
   int grid = nchunks < 2048 ? nchunks : 2048;
   if (is_bf16)
     fused_adamw_kernel<true><<<grid, ADAMW_BLOCK, 0, stream>>>(
@@ -138,6 +141,7 @@ void fused_adamw_launch(float* master, void* params, const void* grads,
         master, params, grads, exp_avg, exp_avg_sq, starts, ends, decay_flags,
         nchunks, lr, b1, b2, eps, wd, step_dev, grad_scale, clip_coef,
         shard_off);
+  return hipGetLastError();
 }
 
 }  // extern "C"

@@ -543,22 +543,25 @@ __global__ __launch_bounds__(256) void attn_bwd_finalize_kernel(
 
 extern "C" {
 
-void attn_bwd_launch(const void* dout, const void* qkv, const void* halo,
-                     const float* rsin, const float* rcos, const void* out,
-                     const float* lse, float* dacc, float* dlook,
-                     float* dhalo, void* dqkv, int B, int N,
-                     int H, int wsz, hipStream_t stream) {
+hipError_t attn_bwd_launch(const void* dout, const void* qkv, const void* halo,
+                           const float* rsin, const float* rcos,
+                           const void* out, const float* lse, float* dacc,
+                           float* dlook, float* dhalo, void* dqkv, int B, int N,
+                           int H, int wsz, hipStream_t stream) {
   dim3 grid(N / wsz, H, B), block(V5_BLOCK);  // 8 waves: 2/SIMD
   size_t lds = 24576 + 131072 + 2048;  // 154 KiB
   attn_bwd_kernel<<<grid, block, lds, stream>>>(
       (const short*)dout, (const short*)qkv, (const short*)halo,
       (const short*)out, lse, dacc, dlook, dhalo, B, N, H, wsz);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return err;
   int gx = (3 * H * (DH / 8) + 255) / 256;
   long long bn_tot = (long long)B * N;
   int gy = (int)(bn_tot < 2048 ? bn_tot : 2048);
   dim3 fin_grid(gx, gy);
   attn_bwd_finalize_kernel<<<fin_grid, 256, 0, stream>>>(
       dacc, dlook, rsin, rcos, (short*)dqkv, B, N, H, wsz);
+  return hipGetLastError();
 }
 
 }  // extern "C"

@@ -371,9 +371,9 @@ __global__ __launch_bounds__(ATTN_BLOCK) void attn_fwd_kernel(
 
 extern "C" {
 
-void attn_fwd_launch(const void* qkv_rot, const void* halo, void* out,
-                     float* lse, int B, int N, int H, int wsz,
-                     hipStream_t stream) {
+hipError_t attn_fwd_launch(const void* qkv_rot, const void* halo, void* out,
+                           float* lse, int B, int N, int H, int wsz,
+                           hipStream_t stream) {
   const int sub_per_win = (wsz + ATTN_WAVES * QB - 1) / (ATTN_WAVES * QB);
   dim3 grid((N / wsz) * sub_per_win, H, B), block(ATTN_BLOCK);
   size_t lds = (size_t)(4 * KT * DH * 2) + (size_t)ATTN_WAVES * QB * KT * 2 +
@@ -381,6 +381,7 @@ void attn_fwd_launch(const void* qkv_rot, const void* halo, void* out,
   attn_fwd_kernel<<<grid, block, lds, stream>>>(
       (const short*)qkv_rot, (const short*)halo, (short*)out, lse, B, N, H,
       wsz);
+  return hipGetLastError();
 }
 
 }  // extern "C"

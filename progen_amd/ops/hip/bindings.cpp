@@ -2,117 +2,134 @@
 //
 // Tensor checks + output allocation here; all device code lives in the
 // .hip translation units (compiled for gfx950 only — no CUDA path).
+//
+// Every entry point that launches a kernel has the same shape: the checks
+// of checks.h in their fixed order (dtype, shape, divisibility, range,
+// device), then a DeviceScope on the first tensor's device, then
+// allocation, then the launcher through LAUNCH, which turns a rejected
+// launch into an exception. What a check demands is read off the kernel's
+// indexing; values that live in device memory (targets, chunk tables, tile
+// lists) cannot be checked here and are noted at the op.
 
 #include <torch/extension.h>
 
-#include <c10/hip/HIPStream.h>
-
+#include "checks.h"
 #include "kernels.h"
 
-namespace {
-
-inline hipStream_t cur_stream() {
-  return c10::hip::getCurrentHIPStream().stream();
-}
-
-inline bool check_dtype(const at::Tensor& t) {
-  TORCH_CHECK(t.scalar_type() == at::kBFloat16 || t.scalar_type() == at::kFloat,
-              "expected bf16 or fp32 tensor");
-  return t.scalar_type() == at::kBFloat16;
-}
-
-}  // namespace
+using namespace chk;
 
 // ---------------------------------------------------------------------------
 // ln_shift
 // ---------------------------------------------------------------------------
 
-std::vector<at::Tensor> ln_shift_fwd(const at::Tensor& x, const at::Tensor& g,
-                                     bool shift, double eps) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 3);
-  bool bf = check_dtype(x);
-  const int B = x.size(0), N = x.size(1), D = x.size(2);
-  TORCH_CHECK(D % 16 == 0, "ln_shift: D must be a multiple of 16");
+// Forward, with or without the fused residual add. With ``res``,
+// s = x + res is formed in-kernel (bf16 rounding identical to an eager
+// add), LN runs on s, and s is returned as the new residual stream — the
+// separate elementwise add disappears. Returns {y, mean, rstd} or
+// {y, s, mean, rstd}.
+static std::vector<at::Tensor> ln_shift_fwd_impl(const char* op,
+                                                 const at::Tensor& x,
+                                                 const at::Tensor* res,
+                                                 const at::Tensor& g,
+                                                 bool shift, double eps) {
+  const bool bf = dtype_bf16_or_fp32(op, ARG(x));
+  dtype_same(op, ARG(g), ARG(x));
+  if (res) dtype_same(op, Arg{"res", *res}, ARG(x));
+  contiguous_rank(op, ARG(x), 3);
+  const int64_t B = x.size(0), N = x.size(1), D = x.size(2);
+  if (res) contiguous_shape(op, Arg{"res", *res}, x.sizes());
+  contiguous_numel(op, ARG(g), D);
+  // the shifted half D/2 must be whole 16 B vectors (8 bf16)
+  multiple_of(op, "D", D, 16);
+  const int Di = extent_int(op, "D", D), Ni = extent_int(op, "N", N);
+  const int R = extent_int(op, "B*N", B * N);
+  same_gpu(op, {ARG(x), ARG(g)});
+  if (res) same_gpu(op, {ARG(x), Arg{"res", *res}});
+
+  DeviceScope dev(x);
   auto y = at::empty_like(x);
-  auto mean = at::empty({(long)B * N}, x.options().dtype(at::kFloat));
+  auto s = res ? at::empty_like(x) : at::Tensor();
+  auto mean = at::empty({B * N}, x.options().dtype(at::kFloat));
   auto rstd = at::empty_like(mean);
-  ln_shift_fwd_launch(x.data_ptr(), nullptr, g.data_ptr(), y.data_ptr(),
-                      nullptr, mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                      B * N, N, D, (float)eps, shift, bf, cur_stream());
+  LAUNCH(op, ln_shift_fwd_launch(
+                 x.data_ptr(), res ? res->data_ptr() : nullptr, g.data_ptr(),
+                 y.data_ptr(), res ? s.data_ptr() : nullptr,
+                 mean.data_ptr<float>(), rstd.data_ptr<float>(), R, Ni, Di,
+                 (float)eps, shift, bf, dev.stream));
+  if (res) return {y, s, mean, rstd};
   return {y, mean, rstd};
 }
 
-// residual-fused variant: s = x + res is formed in-kernel (bf16 rounding
-// identical to an eager add), LN runs on s, and s is returned as the new
-// residual stream — the separate elementwise add disappears.
+std::vector<at::Tensor> ln_shift_fwd(const at::Tensor& x, const at::Tensor& g,
+                                     bool shift, double eps) {
+  return ln_shift_fwd_impl("ln_shift_fwd", x, nullptr, g, shift, eps);
+}
+
 std::vector<at::Tensor> ln_shift_res_fwd(const at::Tensor& x,
                                          const at::Tensor& res,
                                          const at::Tensor& g, bool shift,
                                          double eps) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 3);
-  TORCH_CHECK(res.is_contiguous() && res.sizes() == x.sizes() &&
-              res.scalar_type() == x.scalar_type());
-  bool bf = check_dtype(x);
-  const int B = x.size(0), N = x.size(1), D = x.size(2);
-  TORCH_CHECK(D % 16 == 0, "ln_shift: D must be a multiple of 16");
-  auto y = at::empty_like(x);
-  auto s = at::empty_like(x);
-  auto mean = at::empty({(long)B * N}, x.options().dtype(at::kFloat));
-  auto rstd = at::empty_like(mean);
-  ln_shift_fwd_launch(x.data_ptr(), res.data_ptr(), g.data_ptr(), y.data_ptr(),
-                      s.data_ptr(), mean.data_ptr<float>(),
-                      rstd.data_ptr<float>(), B * N, N, D, (float)eps, shift,
-                      bf, cur_stream());
-  return {y, s, mean, rstd};
+  return ln_shift_fwd_impl("ln_shift_res_fwd", x, &res, g, shift, eps);
+}
+
+// Backward. ``x`` is the tensor the statistics were computed on (the saved
+// summed stream ``s_in`` of the residual-fused variant); ``ds`` (optional)
+// is the gradient flowing into s from its later uses. With the fused
+// variant the returned dx is the gradient of BOTH addends (d(x + res) fans
+// out identically).
+static std::vector<at::Tensor> ln_shift_bwd_impl(
+    const char* op, const at::Tensor& dy, const c10::optional<at::Tensor>& ds,
+    Arg xa, const at::Tensor& g, const at::Tensor& mean,
+    const at::Tensor& rstd, bool shift) {
+  const at::Tensor& x = xa.t;
+  const bool bf = dtype_bf16_or_fp32(op, xa);
+  dtype_same(op, ARG(dy), xa);
+  dtype_same(op, ARG(g), xa);
+  if (ds) dtype_same(op, Arg{"ds", *ds}, xa);
+  dtype_is(op, ARG(mean), at::kFloat);
+  dtype_is(op, ARG(rstd), at::kFloat);
+  contiguous_rank(op, xa, 3);
+  const int64_t B = x.size(0), N = x.size(1), D = x.size(2);
+  contiguous_shape(op, ARG(dy), x.sizes());
+  if (ds) contiguous_shape(op, Arg{"ds", *ds}, x.sizes());
+  contiguous_numel(op, ARG(g), D);
+  contiguous_numel(op, ARG(mean), B * N);
+  contiguous_numel(op, ARG(rstd), B * N);
+  multiple_of(op, "D", D, 16);
+  const int Di = extent_int(op, "D", D), Ni = extent_int(op, "N", N);
+  const int R = extent_int(op, "B*N", B * N);
+  same_gpu(op, {xa, ARG(dy), ARG(g), ARG(mean), ARG(rstd)});
+  if (ds) same_gpu(op, {xa, Arg{"ds", *ds}});
+
+  DeviceScope dev(x);
+  const int nblocks = std::min(R, 1024);  // >=4 blocks/CU for latency hiding
+  auto dx = at::empty_like(x);
+  auto dw_part = at::empty({nblocks, D}, x.options().dtype(at::kFloat));
+  LAUNCH(op, ln_shift_bwd_launch(
+                 dy.data_ptr(), ds ? ds->data_ptr() : nullptr, x.data_ptr(),
+                 g.data_ptr(), mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                 dx.data_ptr(), dw_part.data_ptr<float>(), nblocks, R, Ni, Di,
+                 shift, bf, dev.stream));
+  auto dw = dw_part.sum(0).to(x.scalar_type());
+  return {dx, dw};
 }
 
 std::vector<at::Tensor> ln_shift_bwd(const at::Tensor& dy, const at::Tensor& x,
                                      const at::Tensor& g,
                                      const at::Tensor& mean,
                                      const at::Tensor& rstd, bool shift) {
-  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && x.is_contiguous());
-  bool bf = check_dtype(x);
-  const int B = x.size(0), N = x.size(1), D = x.size(2);
-  const int R = B * N;
-  int nblocks = std::min(R, 1024);  // >=4 blocks/CU for latency hiding
-  auto dx = at::empty_like(x);
-  auto dw_part = at::empty({nblocks, D}, x.options().dtype(at::kFloat));
-  ln_shift_bwd_launch(dy.data_ptr(), nullptr, x.data_ptr(), g.data_ptr(),
-                      mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                      dx.data_ptr(), dw_part.data_ptr<float>(), nblocks, R, N,
-                      D, shift, bf, cur_stream());
-  auto dw = dw_part.sum(0).to(x.scalar_type());
-  return {dx, dw};
+  return ln_shift_bwd_impl("ln_shift_bwd", dy, c10::nullopt, ARG(x), g, mean,
+                           rstd, shift);
 }
 
-// backward of the residual-fused variant: ``s_in`` is the saved summed
-// stream (stats were computed on it); ``ds`` (optional) is the gradient
-// flowing into s from its later uses. The returned dx is the gradient of
-// BOTH addends (d(x + res) fans out identically).
 std::vector<at::Tensor> ln_shift_res_bwd(const at::Tensor& dy,
                                          const c10::optional<at::Tensor>& ds,
                                          const at::Tensor& s_in,
                                          const at::Tensor& g,
                                          const at::Tensor& mean,
                                          const at::Tensor& rstd, bool shift) {
-  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && s_in.is_contiguous());
-  bool bf = check_dtype(s_in);
-  const int B = s_in.size(0), N = s_in.size(1), D = s_in.size(2);
-  const int R = B * N;
-  int nblocks = std::min(R, 1024);
-  const void* ds_ptr = nullptr;
-  if (ds.has_value()) {
-    TORCH_CHECK(ds->is_contiguous() && ds->sizes() == s_in.sizes());
-    ds_ptr = ds->data_ptr();
-  }
-  auto dx = at::empty_like(s_in);
-  auto dw_part = at::empty({nblocks, D}, s_in.options().dtype(at::kFloat));
-  ln_shift_bwd_launch(dy.data_ptr(), ds_ptr, s_in.data_ptr(), g.data_ptr(),
-                      mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                      dx.data_ptr(), dw_part.data_ptr<float>(), nblocks, R, N,
-                      D, shift, bf, cur_stream());
-  auto dw = dw_part.sum(0).to(s_in.scalar_type());
-  return {dx, dw};
+  return ln_shift_bwd_impl("ln_shift_res_bwd", dy, ds, ARG(s_in), g, mean,
+                           rstd, shift);
 }
 
 // ---------------------------------------------------------------------------
@@ -120,77 +137,138 @@ std::vector<at::Tensor> ln_shift_res_bwd(const at::Tensor& dy,
 // ---------------------------------------------------------------------------
 
 at::Tensor glu_fwd(const at::Tensor& h) {
-  TORCH_CHECK(h.is_cuda() && h.is_contiguous());
-  bool bf = check_dtype(h);
-  const int H2 = h.size(-1);
-  TORCH_CHECK(H2 % 16 == 0);
-  long long rows = h.numel() / H2;
+  const char* op = "glu_fwd";
+  const bool bf = dtype_bf16_or_fp32(op, ARG(h));
+  CHK(h.dim() >= 1, op, "h", h.dim(), "must have at least 1 dim");
+  contiguous(op, ARG(h));
+  const int64_t H2 = h.size(-1), rows = leading_rows(h);
+  multiple_of(op, "H2", H2, 16);  // each half is whole 16 B vectors
+  const int H = extent_int(op, "H2", H2) / 2;
+  extent(op, "rows", rows, INT64_MAX);
+  same_gpu(op, {ARG(h)});
+
+  DeviceScope dev(h);
   auto sizes = h.sizes().vec();
-  sizes.back() = H2 / 2;
+  sizes.back() = H;
   auto y = at::empty(sizes, h.options());
-  glu_fwd_launch(h.data_ptr(), y.data_ptr(), rows, H2 / 2, bf, cur_stream());
+  LAUNCH(op, glu_fwd_launch(h.data_ptr(), y.data_ptr(), rows, H, bf,
+                            dev.stream));
   return y;
 }
 
 at::Tensor glu_bwd(const at::Tensor& dy, const at::Tensor& h) {
-  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && h.is_contiguous());
-  bool bf = check_dtype(h);
-  const int H2 = h.size(-1);
-  long long rows = h.numel() / H2;
+  const char* op = "glu_bwd";
+  const bool bf = dtype_bf16_or_fp32(op, ARG(h));
+  dtype_same(op, ARG(dy), ARG(h));
+  CHK(h.dim() >= 1, op, "h", h.dim(), "must have at least 1 dim");
+  contiguous(op, ARG(h));
+  const int64_t H2 = h.size(-1), rows = leading_rows(h);
+  auto dy_sizes = h.sizes().vec();
+  dy_sizes.back() = H2 / 2;
+  contiguous_shape(op, ARG(dy), dy_sizes);
+  multiple_of(op, "H2", H2, 16);
+  const int H = extent_int(op, "H2", H2) / 2;
+  extent(op, "rows", rows, INT64_MAX);
+  same_gpu(op, {ARG(h), ARG(dy)});
+
+  DeviceScope dev(h);
   auto dh = at::empty_like(h);
-  glu_bwd_launch(dy.data_ptr(), h.data_ptr(), dh.data_ptr(), rows, H2 / 2, bf,
-                 cur_stream());
+  LAUNCH(op, glu_bwd_launch(dy.data_ptr(), h.data_ptr(), dh.data_ptr(), rows,
+                            H, bf, dev.stream));
   return dh;
 }
 
 at::Tensor gelu_fwd(const at::Tensor& h) {
-  TORCH_CHECK(h.is_cuda() && h.is_contiguous());
-  bool bf = check_dtype(h);
-  TORCH_CHECK(h.numel() % 8 == 0);
+  const char* op = "gelu_fwd";
+  const bool bf = dtype_bf16_or_fp32(op, ARG(h));
+  contiguous(op, ARG(h));
+  multiple_of(op, "h.numel()", h.numel(), 8);
+  extent(op, "h.numel()", h.numel(), INT64_MAX);
+  same_gpu(op, {ARG(h)});
+
+  DeviceScope dev(h);
   auto y = at::empty_like(h);
-  gelu_fwd_launch(h.data_ptr(), y.data_ptr(), h.numel(), bf, cur_stream());
+  LAUNCH(op, gelu_fwd_launch(h.data_ptr(), y.data_ptr(), h.numel(), bf,
+                             dev.stream));
   return y;
 }
 
 at::Tensor gelu_bwd(const at::Tensor& dy, const at::Tensor& h) {
-  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && h.is_contiguous());
-  bool bf = check_dtype(h);
+  const char* op = "gelu_bwd";
+  const bool bf = dtype_bf16_or_fp32(op, ARG(h));
+  dtype_same(op, ARG(dy), ARG(h));
+  contiguous(op, ARG(h));
+  contiguous_shape(op, ARG(dy), h.sizes());
+  multiple_of(op, "h.numel()", h.numel(), 8);
+  extent(op, "h.numel()", h.numel(), INT64_MAX);
+  same_gpu(op, {ARG(h), ARG(dy)});
+
+  DeviceScope dev(h);
   auto dh = at::empty_like(h);
-  gelu_bwd_launch(dy.data_ptr(), h.data_ptr(), dh.data_ptr(), h.numel(), bf,
-                  cur_stream());
+  LAUNCH(op, gelu_bwd_launch(dy.data_ptr(), h.data_ptr(), dh.data_ptr(),
+                             h.numel(), bf, dev.stream));
   return dh;
 }
 
 // ---------------------------------------------------------------------------
 // cross entropy
+//
+// The VALUES of ``targets`` index a logits row and must lie in [0, V); they
+// live in device memory, so checking them would cost a device read and is
+// left to the caller.
 // ---------------------------------------------------------------------------
+
+// one wave per row, CE_WAVES = 4 rows per block on grid x
+static constexpr int64_t kCeMaxRows = 4 * (int64_t)INT_MAX;
 
 std::vector<at::Tensor> ce_fwd(const at::Tensor& logits,
                                const at::Tensor& targets) {
-  TORCH_CHECK(logits.is_cuda() && logits.is_contiguous());
-  TORCH_CHECK(targets.scalar_type() == at::kLong && targets.is_contiguous());
-  bool bf = check_dtype(logits);
-  const int V = logits.size(-1);
-  long long R = logits.numel() / V;
-  auto sizes = targets.sizes().vec();
-  auto nll = at::empty(sizes, logits.options().dtype(at::kFloat));
+  const char* op = "ce_fwd";
+  const bool bf = dtype_bf16_or_fp32(op, ARG(logits));
+  dtype_is(op, ARG(targets), at::kLong);
+  CHK(logits.dim() >= 1, op, "logits", logits.dim(),
+      "must have at least 1 dim");
+  contiguous(op, ARG(logits));
+  const int64_t R = leading_rows(logits);
+  contiguous_numel(op, ARG(targets), R);
+  const int V = extent_int(op, "V", logits.size(-1));
+  extent(op, "rows", R, kCeMaxRows);
+  same_gpu(op, {ARG(logits), ARG(targets)});
+
+  DeviceScope dev(logits);
+  auto nll = at::empty(targets.sizes(), logits.options().dtype(at::kFloat));
   auto lse = at::empty_like(nll);
-  ce_fwd_launch(logits.data_ptr(), (const long long*)targets.data_ptr<long>(),
-                nll.data_ptr<float>(), lse.data_ptr<float>(), R, V, bf,
-                cur_stream());
+  LAUNCH(op, ce_fwd_launch(logits.data_ptr(),
+                           (const long long*)targets.data_ptr<int64_t>(),
+                           nll.data_ptr<float>(), lse.data_ptr<float>(), R, V,
+                           bf, dev.stream));
   return {nll, lse};
 }
 
 at::Tensor ce_bwd(const at::Tensor& dnll, const at::Tensor& logits,
                   const at::Tensor& targets, const at::Tensor& lse) {
-  TORCH_CHECK(dnll.is_cuda() && dnll.is_contiguous());
-  bool bf = check_dtype(logits);
-  const int V = logits.size(-1);
-  long long R = logits.numel() / V;
+  const char* op = "ce_bwd";
+  const bool bf = dtype_bf16_or_fp32(op, ARG(logits));
+  dtype_is(op, ARG(targets), at::kLong);
+  dtype_is(op, ARG(dnll), at::kFloat);
+  dtype_is(op, ARG(lse), at::kFloat);
+  CHK(logits.dim() >= 1, op, "logits", logits.dim(),
+      "must have at least 1 dim");
+  contiguous(op, ARG(logits));
+  const int64_t R = leading_rows(logits);
+  contiguous_numel(op, ARG(targets), R);
+  contiguous_numel(op, ARG(dnll), R);
+  contiguous_numel(op, ARG(lse), R);
+  const int V = extent_int(op, "V", logits.size(-1));
+  extent(op, "rows", R, kCeMaxRows);
+  same_gpu(op, {ARG(logits), ARG(targets), ARG(dnll), ARG(lse)});
+
+  DeviceScope dev(logits);
   auto dlogits = at::empty_like(logits);
-  ce_bwd_launch(dnll.data_ptr<float>(), logits.data_ptr(),
-                (const long long*)targets.data_ptr<long>(), lse.data_ptr<float>(),
-                dlogits.data_ptr(), R, V, bf, cur_stream());
+  LAUNCH(op, ce_bwd_launch(dnll.data_ptr<float>(), logits.data_ptr(),
+                           (const long long*)targets.data_ptr<int64_t>(),
+                           lse.data_ptr<float>(), dlogits.data_ptr(), R, V, bf,
+                           dev.stream));
   return dlogits;
 }
 
@@ -199,15 +277,22 @@ at::Tensor ce_bwd(const at::Tensor& dnll, const at::Tensor& logits,
 // ---------------------------------------------------------------------------
 
 at::Tensor grad_sumsq(const at::Tensor& grads) {
-  TORCH_CHECK(grads.is_cuda() && grads.is_contiguous());
-  bool bf = grads.scalar_type() == at::kBFloat16;
-  TORCH_CHECK(grads.numel() % (bf ? 8 : 4) == 0);
+  const char* op = "grad_sumsq";
+  const bool bf = dtype_bf16_or_fp32(op, ARG(grads));
+  contiguous(op, ARG(grads));
+  multiple_of(op, "grads.numel()", grads.numel(), bf ? 8 : 4);
+  extent(op, "grads.numel()", grads.numel(), INT64_MAX);
+  same_gpu(op, {ARG(grads)});
+
+  DeviceScope dev(grads);
   auto out = at::zeros({1}, grads.options().dtype(at::kFloat));
-  grad_sumsq_launch(grads.data_ptr(), out.data_ptr<float>(), grads.numel(), bf,
-                    cur_stream());
+  LAUNCH(op, grad_sumsq_launch(grads.data_ptr(), out.data_ptr<float>(),
+                               grads.numel(), bf, dev.stream));
   return out;
 }
 
+// The chunk tables' VALUES live in device memory and are taken on trust:
+// every [start, end) must lie inside [shard_off, shard_off + master.numel()).
 void fused_adamw(at::Tensor& master, at::Tensor& params,
                  const at::Tensor& grads, at::Tensor& exp_avg,
                  at::Tensor& exp_avg_sq, const at::Tensor& chunk_starts,
@@ -215,141 +300,256 @@ void fused_adamw(at::Tensor& master, at::Tensor& params,
                  double lr, double b1, double b2, double eps, double wd,
                  at::Tensor& step_dev, double grad_scale,
                  const at::Tensor& clip_coef, int64_t shard_off) {
-  TORCH_CHECK(step_dev.scalar_type() == at::kInt && step_dev.is_cuda());
-  TORCH_CHECK(master.is_cuda() && master.scalar_type() == at::kFloat);
-  bool bf = params.scalar_type() == at::kBFloat16;
-  fused_adamw_launch(master.data_ptr<float>(), params.data_ptr(),
-                     grads.data_ptr(), exp_avg.data_ptr<float>(),
-                     exp_avg_sq.data_ptr<float>(),
-                     (const long long*)chunk_starts.data_ptr<long>(), (const long long*)chunk_ends.data_ptr<long>(),
-                     chunk_decay.data_ptr<int>(), chunk_starts.size(0),
-                     (float)lr, (float)b1, (float)b2, (float)eps, (float)wd,
-                     step_dev.data_ptr<int>(), (float)grad_scale,
-                     clip_coef.data_ptr<float>(), bf, (long long)shard_off,
-                     cur_stream());
+  const char* op = "fused_adamw";
+  const bool bf = dtype_bf16_or_fp32(op, ARG(params));
+  dtype_same(op, ARG(grads), ARG(params));
+  dtype_is(op, ARG(master), at::kFloat);
+  dtype_is(op, ARG(exp_avg), at::kFloat);
+  dtype_is(op, ARG(exp_avg_sq), at::kFloat);
+  dtype_is(op, ARG(chunk_starts), at::kLong);
+  dtype_is(op, ARG(chunk_ends), at::kLong);
+  dtype_is(op, ARG(chunk_decay), at::kInt);
+  dtype_is(op, ARG(step_dev), at::kInt);
+  dtype_is(op, ARG(clip_coef), at::kFloat);
+  contiguous(op, ARG(params));
+  contiguous(op, ARG(master));
+  contiguous(op, ARG(chunk_starts));
+  contiguous_numel(op, ARG(grads), params.numel());
+  contiguous_numel(op, ARG(exp_avg), master.numel());
+  contiguous_numel(op, ARG(exp_avg_sq), master.numel());
+  contiguous_numel(op, ARG(chunk_ends), chunk_starts.numel());
+  contiguous_numel(op, ARG(chunk_decay), chunk_starts.numel());
+  contiguous_numel(op, ARG(step_dev), 1);
+  contiguous_numel(op, ARG(clip_coef), 1);
+  CHK(shard_off >= 0, op, "shard_off", shard_off, "must be >= 0");
+  CHK(shard_off <= params.numel() - master.numel(), op,
+      "shard_off + master.numel()", shard_off + master.numel(),
+      "must be <= params.numel() = ", params.numel());
+  const int nchunks = extent_int(op, "nchunks", chunk_starts.numel());
+  same_gpu(op, {ARG(params), ARG(grads), ARG(master), ARG(exp_avg),
+                ARG(exp_avg_sq), ARG(chunk_starts), ARG(chunk_ends),
+                ARG(chunk_decay), ARG(step_dev), ARG(clip_coef)});
+
+  DeviceScope dev(params);
+  LAUNCH(op, fused_adamw_launch(
+                 master.data_ptr<float>(), params.data_ptr(), grads.data_ptr(),
+                 exp_avg.data_ptr<float>(), exp_avg_sq.data_ptr<float>(),
+                 (const long long*)chunk_starts.data_ptr<int64_t>(),
+                 (const long long*)chunk_ends.data_ptr<int64_t>(),
+                 chunk_decay.data_ptr<int>(), nchunks, (float)lr, (float)b1,
+                 (float)b2, (float)eps, (float)wd, step_dev.data_ptr<int>(),
+                 (float)grad_scale, clip_coef.data_ptr<float>(), bf,
+                 (long long)shard_off, dev.stream));
 }
 
 // ---------------------------------------------------------------------------
-// local attention
+// local attention (dim_head is fixed at 64)
 // ---------------------------------------------------------------------------
 
 at::Tensor rope_qkv(const at::Tensor& qkv, const at::Tensor& rsin,
                     const at::Tensor& rcos) {
-  TORCH_CHECK(qkv.is_cuda() && qkv.is_contiguous() && qkv.dim() == 3);
-  TORCH_CHECK(qkv.scalar_type() == at::kBFloat16);
-  TORCH_CHECK(rsin.scalar_type() == at::kFloat && rsin.is_contiguous());
-  const int B = qkv.size(0), N = qkv.size(1);
-  const int H = (int)(qkv.size(2) / (3 * 64));
-  TORCH_CHECK(qkv.size(2) == 3LL * H * 64, "rope_qkv: dim_head must be 64");
+  const char* op = "rope_qkv";
+  dtype_is(op, ARG(qkv), at::kBFloat16);
+  dtype_is(op, ARG(rsin), at::kFloat);
+  dtype_is(op, ARG(rcos), at::kFloat);
+  contiguous_rank(op, ARG(qkv), 3);
+  const int64_t B = qkv.size(0), N = qkv.size(1), C = qkv.size(2);
+  rope_table(op, ARG(rsin), N);
+  rope_table(op, ARG(rcos), N);
+  multiple_of(op, "qkv.size(2)", C, 3 * 64);  // (q|k|v) x heads x 64
+  const int Bi = extent_int(op, "B", B), Ni = extent_int(op, "N", N);
+  const int H = extent_int(op, "heads", C / (3 * 64));
+  same_gpu(op, {ARG(qkv), ARG(rsin), ARG(rcos)});
+
+  DeviceScope dev(qkv);
   auto qkv_rot = at::empty_like(qkv);
-  rope_qkv_launch(qkv.data_ptr(), rsin.data_ptr<float>(),
-                  rcos.data_ptr<float>(), qkv_rot.data_ptr(), B, N, H,
-                  cur_stream());
+  LAUNCH(op, rope_qkv_launch(qkv.data_ptr(), rsin.data_ptr<float>(),
+                             rcos.data_ptr<float>(), qkv_rot.data_ptr(), Bi,
+                             Ni, H, dev.stream));
   return qkv_rot;
 }
 
-std::vector<at::Tensor> attn_fwd(const at::Tensor& qkv_rot, long heads,
-                                 long window,
+// ``halo`` (context parallelism): the previous rank's last window of
+// rotated [k|v] replaces window 0's zero lookback (parallel/cp.py).
+// heads and window are scalars, so their range is settled before the
+// shapes that are stated in terms of them.
+std::vector<at::Tensor> attn_fwd(const at::Tensor& qkv_rot, int64_t heads,
+                                 int64_t window,
                                  const c10::optional<at::Tensor>& halo) {
-  TORCH_CHECK(qkv_rot.is_cuda() && qkv_rot.is_contiguous() && qkv_rot.dim() == 3);
-  TORCH_CHECK(qkv_rot.scalar_type() == at::kBFloat16,
-              "attn_fwd: bf16 only (MFMA path)");
-  const int B = qkv_rot.size(0), N = qkv_rot.size(1);
-  const int H = (int)heads, wsz = (int)window;
-  TORCH_CHECK(qkv_rot.size(2) == 3LL * H * 64, "attn: dim_head must be 64");
-  TORCH_CHECK(N % wsz == 0 && wsz % 64 == 0,
-              "attn: seq divisible by window, window divisible by 64");
-  const void* halo_ptr = nullptr;
-  if (halo.has_value()) {
-    // context parallelism: the previous rank's last window of rotated
-    // [k|v] replaces window 0's zero lookback (parallel/cp.py)
-    TORCH_CHECK(halo->is_cuda() && halo->is_contiguous() &&
-                halo->scalar_type() == at::kBFloat16);
-    TORCH_CHECK(halo->dim() == 3 && halo->size(0) == B &&
-                halo->size(1) == wsz && halo->size(2) == 2LL * H * 64,
-                "halo must be (B, wsz, 2*H*64) rotated [k|v]");
-    halo_ptr = halo->data_ptr();
-  }
-  auto out = at::empty({B, N, (long)H * 64}, qkv_rot.options());
-  auto lse = at::empty({B, (long)H, N}, qkv_rot.options().dtype(at::kFloat));
-  attn_fwd_launch(qkv_rot.data_ptr(), halo_ptr, out.data_ptr(),
-                  lse.data_ptr<float>(), B, N, H, wsz, cur_stream());
+  const char* op = "attn_fwd";
+  const int H = extent_int(op, "heads", heads, kGridYZ);
+  const int wsz = extent_int(op, "window", window);
+  dtype_is(op, ARG(qkv_rot), at::kBFloat16);  // MFMA path: bf16 only
+  if (halo) dtype_same(op, Arg{"halo", *halo}, ARG(qkv_rot));
+  contiguous_rank(op, ARG(qkv_rot), 3);
+  const int64_t B = qkv_rot.size(0), N = qkv_rot.size(1);
+  CHK(qkv_rot.size(2) == 3 * heads * 64, op, "qkv_rot.size(2)",
+      qkv_rot.size(2), "must be 3*heads*64 = ", 3 * heads * 64);
+  if (halo)
+    contiguous_shape(op, Arg{"halo", *halo}, {B, window, 2 * heads * 64});
+  multiple_of(op, "window", window, 64);
+  multiple_of(op, "N", N, window);
+  const int Bi = extent_int(op, "B", B, kGridYZ);
+  const int Ni = extent_int(op, "N", N);
+  same_gpu(op, {ARG(qkv_rot)});
+  if (halo) same_gpu(op, {ARG(qkv_rot), Arg{"halo", *halo}});
+
+  DeviceScope dev(qkv_rot);
+  auto out = at::empty({B, N, heads * 64}, qkv_rot.options());
+  auto lse = at::empty({B, heads, N}, qkv_rot.options().dtype(at::kFloat));
+  LAUNCH(op, attn_fwd_launch(qkv_rot.data_ptr(),
+                             halo ? halo->data_ptr() : nullptr, out.data_ptr(),
+                             lse.data_ptr<float>(), Bi, Ni, H, wsz,
+                             dev.stream));
   return {out, lse};
 }
 
 std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& qkv,
-                    const at::Tensor& rsin, const at::Tensor& rcos,
-                    const at::Tensor& out, const at::Tensor& lse, long heads,
-                    long window, const c10::optional<at::Tensor>& halo) {
-  TORCH_CHECK(dout.is_cuda() && dout.is_contiguous());
-  const int B = qkv.size(0), N = qkv.size(1);
-  const int H = (int)heads, wsz = (int)window;
+                                 const at::Tensor& rsin,
+                                 const at::Tensor& rcos, const at::Tensor& out,
+                                 const at::Tensor& lse, int64_t heads,
+                                 int64_t window,
+                                 const c10::optional<at::Tensor>& halo) {
+  const char* op = "attn_bwd";
+  const int H = extent_int(op, "heads", heads, kGridYZ);
+  const int wsz = extent_int(op, "window", window);
+  dtype_is(op, ARG(qkv), at::kBFloat16);
+  dtype_same(op, ARG(dout), ARG(qkv));
+  dtype_same(op, ARG(out), ARG(qkv));
+  if (halo) dtype_same(op, Arg{"halo", *halo}, ARG(qkv));
+  dtype_is(op, ARG(lse), at::kFloat);
+  dtype_is(op, ARG(rsin), at::kFloat);
+  dtype_is(op, ARG(rcos), at::kFloat);
+  contiguous_rank(op, ARG(qkv), 3);
+  const int64_t B = qkv.size(0), N = qkv.size(1);
+  CHK(qkv.size(2) == 3 * heads * 64, op, "qkv.size(2)", qkv.size(2),
+      "must be 3*heads*64 = ", 3 * heads * 64);
+  contiguous_shape(op, ARG(out), {B, N, heads * 64});
+  contiguous_shape(op, ARG(dout), {B, N, heads * 64});
+  contiguous_shape(op, ARG(lse), {B, heads, N});
+  rope_table(op, ARG(rsin), N);
+  rope_table(op, ARG(rcos), N);
+  if (halo)
+    contiguous_shape(op, Arg{"halo", *halo}, {B, window, 2 * heads * 64});
+  multiple_of(op, "window", window, 64);
+  multiple_of(op, "N", N, window);
+  const int Bi = extent_int(op, "B", B, kGridYZ);
+  const int Ni = extent_int(op, "N", N);
+  same_gpu(op, {ARG(qkv), ARG(dout), ARG(out), ARG(lse), ARG(rsin),
+                ARG(rcos)});
+  if (halo) same_gpu(op, {ARG(qkv), Arg{"halo", *halo}});
+
+  DeviceScope dev(qkv);
   // plain-store accumulators: every element is written (dq by its row
   // owner; own/lookback k,v by their single writing block) -> no zeroing
-  auto dacc = at::empty_like(qkv, qkv.options().dtype(at::kFloat));
-  auto dlook = at::empty({(long)B, (long)N, 2L * H * 64},
-                         qkv.options().dtype(at::kFloat));
+  const auto f32 = qkv.options().dtype(at::kFloat);
+  auto dacc = at::empty_like(qkv, f32);
+  auto dlook = at::empty({B, N, 2 * heads * 64}, f32);
   auto dqkv = at::empty_like(qkv);
-  const void* halo_ptr = nullptr;
-  float* dhalo_ptr = nullptr;
-  at::Tensor dhalo;
-  if (halo.has_value()) {
-    TORCH_CHECK(halo->is_cuda() && halo->is_contiguous() &&
-                halo->scalar_type() == at::kBFloat16);
-    halo_ptr = halo->data_ptr();
-    // window-0 slices write every element of their bands (plain
-    // stores), so no zeroing needed here either
-    dhalo = at::empty({(long)B, (long)wsz, 2L * H * 64},
-                      qkv.options().dtype(at::kFloat));
-    dhalo_ptr = dhalo.data_ptr<float>();
-  }
-  attn_bwd_launch(dout.data_ptr(), qkv.data_ptr(), halo_ptr,
-                  rsin.data_ptr<float>(), rcos.data_ptr<float>(),
-                  out.data_ptr(), lse.data_ptr<float>(),
-                  dacc.data_ptr<float>(), dlook.data_ptr<float>(), dhalo_ptr,
-                  dqkv.data_ptr(), B, N, H, wsz, cur_stream());
-  if (halo.has_value()) return {dqkv, dhalo};
+  // window-0 slices write every element of their bands (plain stores), so
+  // no zeroing needed here either
+  auto dhalo = halo ? at::empty({B, window, 2 * heads * 64}, f32)
+                    : at::Tensor();
+  LAUNCH(op, attn_bwd_launch(
+                 dout.data_ptr(), qkv.data_ptr(),
+                 halo ? halo->data_ptr() : nullptr, rsin.data_ptr<float>(),
+                 rcos.data_ptr<float>(), out.data_ptr(), lse.data_ptr<float>(),
+                 dacc.data_ptr<float>(), dlook.data_ptr<float>(),
+                 halo ? dhalo.data_ptr<float>() : nullptr, dqkv.data_ptr(), Bi,
+                 Ni, H, wsz, dev.stream));
+  if (halo) return {dqkv, dhalo};
   return {dqkv};
 }
 
+// ---------------------------------------------------------------------------
+// SGU: blocks of 256 rows x 64 channels on grid (N/256, D/64, B)
+// ---------------------------------------------------------------------------
+
 std::vector<at::Tensor> sgu_fwd(const at::Tensor& xa, const at::Tensor& g_ln,
                                 const at::Tensor& w, const at::Tensor& bias) {
-  TORCH_CHECK(xa.is_cuda() && xa.is_contiguous() && xa.dim() == 3);
-  TORCH_CHECK(xa.scalar_type() == at::kBFloat16 &&
-              g_ln.scalar_type() == at::kBFloat16 &&
-              w.scalar_type() == at::kBFloat16);
-  const int B = xa.size(0), N = xa.size(1), D = xa.size(2);
-  TORCH_CHECK(N % 256 == 0 && D % 64 == 0, "sgu_fwd: N%256, D%64 required");
-  TORCH_CHECK(w.is_contiguous() && w.size(0) == N && w.size(1) == N);
+  const char* op = "sgu_fwd";
+  dtype_is(op, ARG(xa), at::kBFloat16);
+  dtype_same(op, ARG(g_ln), ARG(xa));
+  dtype_same(op, ARG(w), ARG(xa));
+  contiguous_rank(op, ARG(xa), 3);
+  const int64_t B = xa.size(0), N = xa.size(1), D = xa.size(2);
+  contiguous_shape(op, ARG(g_ln), xa.sizes());
+  contiguous_shape(op, ARG(w), {N, N});
+  // any dtype or layout: converted to contiguous fp32 below
+  CHK(bias.numel() == N, op, "bias", bias.numel(), "must have ", N,
+      " elements");
+  multiple_of(op, "N", N, 256);
+  multiple_of(op, "D", D, 64);
+  const int Bi = extent_int(op, "B", B, kGridYZ);
+  const int Ni = extent_int(op, "N", N);
+  const int Di = extent_int(op, "D", D, 64 * kGridYZ);
+  same_gpu(op, {ARG(xa), ARG(g_ln), ARG(w), ARG(bias)});
+
+  DeviceScope dev(xa);
   auto bias_f = bias.to(at::kFloat).contiguous().view({-1});
   auto out = at::empty_like(xa);
   auto gate_out = at::empty_like(xa);
-  sgu_fwd_launch(xa.data_ptr(), g_ln.data_ptr(), w.data_ptr(),
-                 bias_f.data_ptr<float>(), out.data_ptr(),
-                 gate_out.data_ptr(), B, N, D, cur_stream());
+  LAUNCH(op, sgu_fwd_launch(xa.data_ptr(), g_ln.data_ptr(), w.data_ptr(),
+                            bias_f.data_ptr<float>(), out.data_ptr(),
+                            gate_out.data_ptr(), Bi, Ni, Di, dev.stream));
   return {out, gate_out};
 }
 
 at::Tensor sgu_dgate(const at::Tensor& t_in, const at::Tensor& w) {
-  const int B = t_in.size(0), N = t_in.size(1), D = t_in.size(2);
+  const char* op = "sgu_dgate";
+  dtype_is(op, ARG(t_in), at::kBFloat16);
+  dtype_same(op, ARG(w), ARG(t_in));
+  contiguous_rank(op, ARG(t_in), 3);
+  const int64_t B = t_in.size(0), N = t_in.size(1), D = t_in.size(2);
+  contiguous_shape(op, ARG(w), {N, N});
+  // a block stages a 64 x 256 slab of w and 64 x 64 tiles of t_in
+  multiple_of(op, "N", N, 256);
+  multiple_of(op, "D", D, 64);
+  const int Bi = extent_int(op, "B", B, kGridYZ);
+  const int Ni = extent_int(op, "N", N);
+  const int Di = extent_int(op, "D", D, 64 * kGridYZ);
+  same_gpu(op, {ARG(t_in), ARG(w)});
+
+  DeviceScope dev(t_in);
   auto dg = at::empty_like(t_in);
-  sgu_dgate_launch(t_in.data_ptr(), w.data_ptr(), dg.data_ptr(), B, N, D,
-                   cur_stream());
+  LAUNCH(op, sgu_dgate_launch(t_in.data_ptr(), w.data_ptr(), dg.data_ptr(),
+                              Bi, Ni, Di, dev.stream));
   return dg;
 }
 
+// The tile lists' VALUES live in device memory and are taken on trust:
+// every (tri_m, tri_k) names a 64 x 64 tile of the (N, N) result, so each
+// index must lie in [0, N/64).
 at::Tensor sgu_dw(const at::Tensor& t_in, const at::Tensor& g_ln,
                   const at::Tensor& tri_m, const at::Tensor& tri_k) {
-  const int B = t_in.size(0), N = t_in.size(1), D = t_in.size(2);
-  TORCH_CHECK(tri_m.scalar_type() == at::kInt && tri_m.is_cuda());
-  auto dw = at::zeros({(long)N, (long)N},
-                      t_in.options().dtype(at::kFloat));
-  sgu_dw_launch(t_in.data_ptr(), g_ln.data_ptr(), dw.data_ptr<float>(),
-                tri_m.data_ptr<int>(), tri_k.data_ptr<int>(),
-                tri_m.size(0), B, N, D, cur_stream());
+  const char* op = "sgu_dw";
+  dtype_is(op, ARG(t_in), at::kBFloat16);
+  dtype_same(op, ARG(g_ln), ARG(t_in));
+  dtype_is(op, ARG(tri_m), at::kInt);
+  dtype_is(op, ARG(tri_k), at::kInt);
+  contiguous_rank(op, ARG(t_in), 3);
+  const int64_t B = t_in.size(0), N = t_in.size(1), D = t_in.size(2);
+  contiguous_shape(op, ARG(g_ln), t_in.sizes());
+  contiguous(op, ARG(tri_m));
+  contiguous_numel(op, ARG(tri_k), tri_m.numel());
+  // one wave per 64 x 64 tile, reducing D in MFMA steps of 32 channels,
+  // 768-channel chunks on grid y
+  multiple_of(op, "N", N, 64);
+  multiple_of(op, "D", D, 32);
+  const int ntri = extent_int(op, "tri_m.numel()", tri_m.numel());
+  const int Bi = extent_int(op, "B", B, kGridYZ);
+  const int Ni = extent_int(op, "N", N);
+  const int Di = extent_int(op, "D", D, 768 * kGridYZ);
+  same_gpu(op, {ARG(t_in), ARG(g_ln), ARG(tri_m), ARG(tri_k)});
+
+  DeviceScope dev(t_in);
+  auto dw = at::zeros({N, N}, t_in.options().dtype(at::kFloat));
+  LAUNCH(op, sgu_dw_launch(t_in.data_ptr(), g_ln.data_ptr(),
+                           dw.data_ptr<float>(), tri_m.data_ptr<int>(),
+                           tri_k.data_ptr<int>(), ntri, Bi, Ni, Di,
+                           dev.stream));
   return dw;
 }
-
 
 // ---------------------------------------------------------------------------
 // host-side CRC-32C, slicing-by-8 (TFRecord framing; progen_amd/data.py).
@@ -402,34 +602,58 @@ uint32_t crc32c_host(py::bytes data) {
 }
 
 at::Tensor colsum(const at::Tensor& dy) {
-  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && dy.dim() == 2 &&
-              dy.scalar_type() == at::kBFloat16);
-  TORCH_CHECK(dy.size(1) % 8 == 0, "colsum: C % 8");
+  const char* op = "colsum";
+  dtype_is(op, ARG(dy), at::kBFloat16);
+  contiguous_rank(op, ARG(dy), 2);
+  multiple_of(op, "C", dy.size(1), 8);
+  extent(op, "R", dy.size(0), INT_MAX);  // the launcher caps grid y by (int)R
+  const int C = extent_int(op, "C", dy.size(1));
+  same_gpu(op, {ARG(dy)});
+
+  DeviceScope dev(dy);
   auto out = at::zeros({dy.size(1)}, dy.options().dtype(at::kFloat));
-  colsum_launch(dy.data_ptr(), out.data_ptr<float>(), dy.size(0),
-                (int)dy.size(1), cur_stream());
+  LAUNCH(op, colsum_launch(dy.data_ptr(), out.data_ptr<float>(), dy.size(0),
+                           C, dev.stream));
   return out;
 }
 
 at::Tensor fp8_quantize(const at::Tensor& t, const at::Tensor& scale) {
-  TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
-              t.scalar_type() == at::kBFloat16);
-  TORCH_CHECK(t.numel() % 8 == 0, "fp8_quantize: numel % 8");
-  TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == at::kFloat);
+  const char* op = "fp8_quantize";
+  dtype_is(op, ARG(t), at::kBFloat16);
+  dtype_is(op, ARG(scale), at::kFloat);
+  contiguous(op, ARG(t));
+  contiguous_numel(op, ARG(scale), 1);
+  multiple_of(op, "t.numel()", t.numel(), 8);
+  extent(op, "t.numel()", t.numel(), INT64_MAX);
+  same_gpu(op, {ARG(t), ARG(scale)});
+
+  DeviceScope dev(t);
   auto out = at::empty_like(t, t.options().dtype(at::kFloat8_e4m3fn));
-  quant_e4m3_launch(t.data_ptr(), out.data_ptr(), scale.data_ptr<float>(),
-                    t.numel(), cur_stream());
+  LAUNCH(op, quant_e4m3_launch(t.data_ptr(), out.data_ptr(),
+                               scale.data_ptr<float>(), t.numel(),
+                               dev.stream));
   return out;
 }
 
 at::Tensor fp8_quantize_t(const at::Tensor& w, const at::Tensor& scale) {
-  TORCH_CHECK(w.is_cuda() && w.is_contiguous() && w.dim() == 2 &&
-              w.scalar_type() == at::kBFloat16);
-  TORCH_CHECK(w.size(0) % 2 == 0, "fp8_quantize_t: rows % 2");
+  const char* op = "fp8_quantize_t";
+  dtype_is(op, ARG(w), at::kBFloat16);
+  dtype_is(op, ARG(scale), at::kFloat);
+  contiguous_rank(op, ARG(w), 2);
+  contiguous_numel(op, ARG(scale), 1);
+  multiple_of(op, "rows", w.size(0), 2);  // outputs are stored in pairs
+  const int Nr = extent_int(op, "rows", w.size(0));
+  const int Kc = extent_int(op, "cols", w.size(1));
+  // the launcher counts 64 x 64 tiles in int
+  extent(op, "tiles", ((w.size(0) + 63) / 64) * ((w.size(1) + 63) / 64),
+         INT_MAX);
+  same_gpu(op, {ARG(w), ARG(scale)});
+
+  DeviceScope dev(w);
   auto out = at::empty({w.size(1), w.size(0)},
                        w.options().dtype(at::kFloat8_e4m3fn));
-  quant_e4m3_t_launch(w.data_ptr(), out.data_ptr(), scale.data_ptr<float>(),
-                      (int)w.size(0), (int)w.size(1), cur_stream());
+  LAUNCH(op, quant_e4m3_t_launch(w.data_ptr(), out.data_ptr(),
+                                 scale.data_ptr<float>(), Nr, Kc, dev.stream));
   return out;
 }
 

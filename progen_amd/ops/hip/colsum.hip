@@ -33,8 +33,8 @@ __global__ __launch_bounds__(CS_BLOCK) void colsum_kernel(
 
 extern "C" {
 
-void colsum_launch(const void* dy, float* out, long long R, int C,
-                   hipStream_t stream) {
+hipError_t colsum_launch(const void* dy, float* out, long long R, int C,
+                         hipStream_t stream) {
   const int gx = (C + CS_COLS - 1) / CS_COLS;
   // >> 256 blocks to fill the chip (the first cut capped at 256 = one
   // 4-wave block per CU and ran latency-bound, SLOWER than torch's
@@ -45,6 +45,7 @@ void colsum_launch(const void* dy, float* out, long long R, int C,
   if (gy > (int)R) gy = (int)R;
   dim3 grid(gx, gy);
   colsum_kernel<<<grid, CS_BLOCK, 0, stream>>>((const short*)dy, out, R, C);
+  return hipGetLastError();
 }
 
 }  // extern "C"

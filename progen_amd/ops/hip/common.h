@@ -98,12 +98,3 @@ __device__ __forceinline__ void gelu_tanh_both(float x, float* val,
   *val = 0.5f * x * (1.0f + t);
   *grad = 0.5f * (1.0f + t) + 0.5f * x * (1.0f - t * t) * dinner;
 }
-
-#define HIP_CHECK_LAST()                                                      \
-  do {                                                                        \
-    hipError_t e_ = hipGetLastError();                                        \
-    if (e_ != hipSuccess) {                                                   \
-      printf("HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__,     \
-             __LINE__);                                                       \
-    }                                                                         \
-  } while (0)

@@ -72,9 +72,9 @@ __global__ __launch_bounds__(CE_BLOCK) void ce_bwd_kernel(
 
 extern "C" {
 
-void ce_fwd_launch(const void* logits, const long long* targets, float* nll,
-                   float* lse, long long R, int V, bool is_bf16,
-                   hipStream_t stream) {
+hipError_t ce_fwd_launch(const void* logits, const long long* targets,
+                         float* nll, float* lse, long long R, int V,
+                         bool is_bf16, hipStream_t stream) {
   long long blocks = (R + CE_WAVES - 1) / CE_WAVES;
   if (is_bf16)
     ce_fwd_kernel<true><<<blocks, CE_BLOCK, 0, stream>>>(logits, targets, nll,
@@ -82,11 +82,13 @@ void ce_fwd_launch(const void* logits, const long long* targets, float* nll,
   else
     ce_fwd_kernel<false><<<blocks, CE_BLOCK, 0, stream>>>(logits, targets, nll,
                                                           lse, R, V);
+  return hipGetLastError();
 }
 
-void ce_bwd_launch(const float* dnll, const void* logits,
-                   const long long* targets, const float* lse, void* dlogits,
-                   long long R, int V, bool is_bf16, hipStream_t stream) {
+hipError_t ce_bwd_launch(const float* dnll, const void* logits,
+                         const long long* targets, const float* lse,
+                         void* dlogits, long long R, int V, bool is_bf16,
+                         hipStream_t stream) {
   long long blocks = (R + CE_WAVES - 1) / CE_WAVES;
   if (is_bf16)
     ce_bwd_kernel<true><<<blocks, CE_BLOCK, 0, stream>>>(dnll, logits, targets,
@@ -94,6 +96,7 @@ void ce_bwd_launch(const float* dnll, const void* logits,
   else
     ce_bwd_kernel<false><<<blocks, CE_BLOCK, 0, stream>>>(dnll, logits, targets,
                                                           lse, dlogits, R, V);
+  return hipGetLastError();
 }
 
 }  // extern "C"

@@ -87,21 +87,23 @@ __global__ __launch_bounds__(QBLOCK) void quant_e4m3_t_kernel(
 
 extern "C" {
 
-void quant_e4m3_launch(const void* in, void* out, const float* scale,
-                       long long numel, hipStream_t stream) {
+hipError_t quant_e4m3_launch(const void* in, void* out, const float* scale,
+                             long long numel, hipStream_t stream) {
   long long n8 = numel / 8;
   int grid = (int)((n8 + QBLOCK - 1) / QBLOCK);
   if (grid > 4096) grid = 4096;
   quant_e4m3_kernel<<<grid, QBLOCK, 0, stream>>>(
       (const short*)in, (unsigned char*)out, scale, n8);
+  return hipGetLastError();
 }
 
-void quant_e4m3_t_launch(const void* in, void* out, const float* scale,
-                         int Nr, int Kc, hipStream_t stream) {
+hipError_t quant_e4m3_t_launch(const void* in, void* out, const float* scale,
+                               int Nr, int Kc, hipStream_t stream) {
   int tiles = ((Nr + TT - 1) / TT) * ((Kc + TT - 1) / TT);
   int grid = tiles < 4096 ? tiles : 4096;
   quant_e4m3_t_kernel<<<grid, QBLOCK, 0, stream>>>(
       (const short*)in, (unsigned char*)out, scale, Nr, Kc);
+  return hipGetLastError();
 }
 
 }  // extern "C"

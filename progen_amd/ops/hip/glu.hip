@@ -117,8 +117,8 @@ static inline dim3 glu_grid2(long long rows, int Hv) {
 
 extern "C" {
 
-void glu_fwd_launch(const void* h, void* y, long long rows, int H,
-                    bool is_bf16, hipStream_t stream) {
+hipError_t glu_fwd_launch(const void* h, void* y, long long rows, int H,
+                          bool is_bf16, hipStream_t stream) {
   if (is_bf16) {
     int Hv = H / 8;
     glu_fwd_kernel<bf16x8, true><<<glu_grid2(rows, Hv), GLU_BLOCK, 0, stream>>>(
@@ -128,10 +128,12 @@ void glu_fwd_launch(const void* h, void* y, long long rows, int H,
     glu_fwd_kernel<f32x4, false><<<glu_grid2(rows, Hv), GLU_BLOCK, 0, stream>>>(
         (const f32x4*)h, (f32x4*)y, rows, Hv);
   }
+  return hipGetLastError();
 }
 
-void glu_bwd_launch(const void* dy, const void* h, void* dh, long long rows,
-                    int H, bool is_bf16, hipStream_t stream) {
+hipError_t glu_bwd_launch(const void* dy, const void* h, void* dh,
+                          long long rows, int H, bool is_bf16,
+                          hipStream_t stream) {
   if (is_bf16) {
     int Hv = H / 8;
     glu_bwd_kernel<bf16x8, true><<<glu_grid2(rows, Hv), GLU_BLOCK, 0, stream>>>(
@@ -141,10 +143,11 @@ void glu_bwd_launch(const void* dy, const void* h, void* dh, long long rows,
     glu_bwd_kernel<f32x4, false><<<glu_grid2(rows, Hv), GLU_BLOCK, 0, stream>>>(
         (const f32x4*)dy, (const f32x4*)h, (f32x4*)dh, rows, Hv);
   }
+  return hipGetLastError();
 }
 
-void gelu_fwd_launch(const void* h, void* y, long long total_elems,
-                     bool is_bf16, hipStream_t stream) {
+hipError_t gelu_fwd_launch(const void* h, void* y, long long total_elems,
+                           bool is_bf16, hipStream_t stream) {
   long long tv = total_elems / (is_bf16 ? 8 : 4);
   if (is_bf16)
     gelu_fwd_kernel<bf16x8, true><<<glu_grid(tv), GLU_BLOCK, 0, stream>>>(
@@ -152,10 +155,12 @@ void gelu_fwd_launch(const void* h, void* y, long long total_elems,
   else
     gelu_fwd_kernel<f32x4, false><<<glu_grid(tv), GLU_BLOCK, 0, stream>>>(
         (const f32x4*)h, (f32x4*)y, tv);
+  return hipGetLastError();
 }
 
-void gelu_bwd_launch(const void* dy, const void* h, void* dh,
-                     long long total_elems, bool is_bf16, hipStream_t stream) {
+hipError_t gelu_bwd_launch(const void* dy, const void* h, void* dh,
+                           long long total_elems, bool is_bf16,
+                           hipStream_t stream) {
   long long tv = total_elems / (is_bf16 ? 8 : 4);
   if (is_bf16)
     gelu_bwd_kernel<bf16x8, true><<<glu_grid(tv), GLU_BLOCK, 0, stream>>>(
@@ -163,6 +168,7 @@ void gelu_bwd_launch(const void* dy, const void* h, void* dh,
   else
     gelu_bwd_kernel<f32x4, false><<<glu_grid(tv), GLU_BLOCK, 0, stream>>>(
         (const f32x4*)dy, (const f32x4*)h, (f32x4*)dh, tv);
+  return hipGetLastError();
 }
 
 }  // extern "C"

@@ -359,10 +359,10 @@ __global__ __launch_bounds__(LN_BLOCK) void ln_shift_bwd_kernel(
 
 extern "C" {
 
-void ln_shift_fwd_launch(const void* x, const void* res, const void* g,
-                         void* y, void* s_out, float* mean, float* rstd,
-                         int R, int N, int D, float eps, bool shift,
-                         bool is_bf16, hipStream_t stream) {
+hipError_t ln_shift_fwd_launch(const void* x, const void* res, const void* g,
+                               void* y, void* s_out, float* mean, float* rstd,
+                               int R, int N, int D, float eps, bool shift,
+                               bool is_bf16, hipStream_t stream) {
   dim3 grid(R), block(LN_BLOCK);
 #define LNF(VEC, SH, BF, RS)                                              \
   ln_shift_fwd_kernel<VEC, SH, BF, RS><<<grid, block, 0, stream>>>(       \
@@ -378,12 +378,14 @@ void ln_shift_fwd_launch(const void* x, const void* res, const void* g,
     else       { if (res) LNF(f32x4, false, false, true); else LNF(f32x4, false, false, false); }
   }
 #undef LNF
+  return hipGetLastError();
 }
 
-void ln_shift_bwd_launch(const void* dy, const void* ds, const void* x,
-                         const void* g, const float* mean, const float* rstd,
-                         void* dx, float* dw_part, int nblocks, int R, int N,
-                         int D, bool shift, bool is_bf16, hipStream_t stream) {
+hipError_t ln_shift_bwd_launch(const void* dy, const void* ds, const void* x,
+                               const void* g, const float* mean,
+                               const float* rstd, void* dx, float* dw_part,
+                               int nblocks, int R, int N, int D, bool shift,
+                               bool is_bf16, hipStream_t stream) {
   dim3 grid(nblocks), block(LN_BLOCK);
   size_t lds = (size_t)D * 4 + LN_WAVES * 4 + 16;
 #define LNB(VEC, SH, BF, WDS)                                             \
@@ -400,6 +402,7 @@ void ln_shift_bwd_launch(const void* dy, const void* ds, const void* x,
     else       { if (ds) LNB(f32x4, false, false, true); else LNB(f32x4, false, false, false); }
   }
 #undef LNB
+  return hipGetLastError();
 }
 
 }  // extern "C"

@@ -56,14 +56,16 @@ __global__ __launch_bounds__(256) void rope_qkv_kernel(
 
 extern "C" {
 
-void rope_qkv_launch(const void* qkv, const float* rsin, const float* rcos,
-                     void* qkv_rot, int B, int N, int H, hipStream_t stream) {
+hipError_t rope_qkv_launch(const void* qkv, const float* rsin,
+                           const float* rcos, void* qkv_rot, int B, int N,
+                           int H, hipStream_t stream) {
   int gx = (3 * H * (DH / 8) + 255) / 256;
   long long bn = (long long)B * N;
   int gy = (int)(bn < 2048 ? bn : 2048);
   dim3 grid(gx, gy);
   rope_qkv_kernel<<<grid, 256, 0, stream>>>((const short*)qkv, rsin, rcos,
                                             (short*)qkv_rot, B, N, H);
+  return hipGetLastError();
 }
 
 }  // extern "C"

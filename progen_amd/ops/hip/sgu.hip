@@ -348,30 +348,33 @@ __global__ __launch_bounds__(WAVE) void sgu_dw_kernel(
 
 extern "C" {
 
-void sgu_fwd_launch(const void* xa, const void* g_ln, const void* w,
-                    const float* bias, void* out, void* gate_out, int B,
-                    int N, int D, hipStream_t stream) {
+hipError_t sgu_fwd_launch(const void* xa, const void* g_ln, const void* w,
+                          const float* bias, void* out, void* gate_out, int B,
+                          int N, int D, hipStream_t stream) {
   dim3 grid(N / 256, D / 64, B), block(SGU_BLOCK);
   sgu_fwd_kernel<<<grid, block, 8192, stream>>>(
       (const short*)xa, (const short*)g_ln, (const short*)w, bias,
       (short*)out, (short*)gate_out, B, N, D);
+  return hipGetLastError();
 }
 
-void sgu_dgate_launch(const void* t_in, const void* w, void* dg, int B, int N,
-                      int D, hipStream_t stream) {
+hipError_t sgu_dgate_launch(const void* t_in, const void* w, void* dg, int B,
+                            int N, int D, hipStream_t stream) {
   dim3 grid(N / 256, D / 64, B), block(SGU_BLOCK);
   size_t lds = 8192 + 32768;  // linear [m][d] t image + [m][k] W image
   sgu_dgate_kernel<<<grid, block, lds, stream>>>(
       (const short*)t_in, (const short*)w, (short*)dg, B, N, D);
+  return hipGetLastError();
 }
 
-void sgu_dw_launch(const void* t_in, const void* g_ln, float* dw,
-                   const int* tri_m, const int* tri_k, int ntri, int B, int N,
-                   int D, hipStream_t stream) {
+hipError_t sgu_dw_launch(const void* t_in, const void* g_ln, float* dw,
+                         const int* tri_m, const int* tri_k, int ntri, int B,
+                         int N, int D, hipStream_t stream) {
   int dchunks = (D + DW_DCHUNK - 1) / DW_DCHUNK;
   dim3 grid(ntri, dchunks, B), block(WAVE);
   sgu_dw_kernel<<<grid, block, 0, stream>>>(
       (const short*)t_in, (const short*)g_ln, dw, tri_m, tri_k, B, N, D);
+  return hipGetLastError();
 }
 
 }  // extern "C"

@@ -544,3 +544,44 @@ def test_fused_adamw_nonfinite_skip():
     assert int(o.step_dev.item()) == 1
     assert not torch.equal(o.master, master0)
     assert torch.isfinite(o.master).all()
+
+
+# ---------------------------------------------------------------------------
+# device guard: tensors on a device other than the current one
+# ---------------------------------------------------------------------------
+
+def test_ops_follow_their_tensors_device():
+    """Each entry point launches on its tensors' device and stream, not on
+    the current device's: cuda:1 inputs while cuda:0 is current."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two GPUs: runs kernels on cuda:1 with cuda:0 current")
+    d1 = torch.device("cuda:1")
+    torch.cuda.set_device(0)
+    torch.manual_seed(31)
+    x = torch.randn(1, 64, 128, device=d1, dtype=torch.bfloat16,
+                    requires_grad=True)
+    g = torch.randn(128, device=d1, dtype=torch.bfloat16, requires_grad=True)
+    h = torch.randn(1, 64, 256, device=d1, dtype=torch.bfloat16,
+                    requires_grad=True)
+
+    y = OF.ln_shift(x, g, shift=True)
+    z = OF.glu_gelu(h)
+    dy, dz = torch.randn_like(y), torch.randn_like(z)
+    torch.autograd.backward([y, z], [dy, dz])
+    torch.cuda.synchronize(d1)
+    assert torch.cuda.current_device() == 0
+    assert y.device == d1 and z.device == d1
+
+    x32 = x.detach().float().cpu().requires_grad_(True)
+    g32 = g.detach().float().cpu().requires_grad_(True)
+    h32 = h.detach().float().cpu().requires_grad_(True)
+    y32 = R.ln_shift(x32, g32, shift=True)
+    z32 = R.glu_gelu(h32)
+    torch.autograd.backward([y32, z32], [dy.float().cpu(), dz.float().cpu()])
+
+    tol = 2e-2  # the bf16 tolerance of the single-device tests above
+    assert rel_err(y, y32) < tol
+    assert rel_err(z, z32) < tol
+    assert rel_err(x.grad, x32.grad) < tol * 3
+    assert rel_err(g.grad, g32.grad) < tol * 3
+    assert rel_err(h.grad, h32.grad) < tol * 3
