@@ -27,6 +27,7 @@ import torch
 import torch.nn.functional as F
 
 from .models.progen import ProGenBase
+from .ops import functional as OF
 from .ops import reference as R
 
 
@@ -262,9 +263,57 @@ def forward_step_static(model: ProGenBase, token: torch.Tensor,
     # increments it (in-graph when captured)
 
 
+@torch.no_grad()
+def forward_step_fused(model: ProGenBase, token: torch.Tensor,
+                       cache: DecodeCache,
+                       pos_dev: torch.Tensor) -> torch.Tensor:
+    """Decode step on the fused decode kernels: same contract as
+    ``forward_step_static`` (position from the 0-dim int64 ``pos_dev``,
+    same ``DecodeCache``, position NOT advanced), but every non-GEMM op of
+    a branch is one of three ops — ``OF.decode_ln_shift``,
+    ``OF.decode_attention``, ``OF.decode_sgu`` (ops/hip/decode_*.hip on a
+    GPU, ops/reference.py on CPU) — plus the existing GLU/GELU kernel.
+    By the code that is 8 launches per GLU layer and 10 per SGU layer.
+
+    The branch output is carried into the next ``decode_ln_shift`` as its
+    residual, as in ``ProGenBase.forward``; the final norm consumes the
+    last one. No workgroup of any kernel waits on another, so the step is
+    as capturable and replayable as the static one."""
+    cfg = model.cfg
+    if model.rotary_sin.dtype != torch.float32:
+        sin, cos = R.fixed_pos_embedding(cfg.seq_len, cfg.dim_head,
+                                         device=model.rotary_sin.device)
+        model.rotary_sin, model.rotary_cos = sin, cos
+    sin, cos = model.rotary_sin, model.rotary_cos
+    h = model.embed(token.long().reshape(-1))           # (B, dim), updated in place
+    r = None
+    for li, (attn, ff) in enumerate(model.layers):
+        y = OF.decode_ln_shift(h, r, attn.norm_weight, cache.attn_prev[li],
+                               shift=attn.shift_tokens)
+        qkv = F.linear(y, attn.to_qkv.weight)
+        out = OF.decode_attention(qkv, sin, cos, pos_dev, cache.k[li],
+                                  cache.v[li], attn.window_size)
+        a = F.linear(out, attn.to_out.weight, attn.to_out.bias)
+
+        y = OF.decode_ln_shift(h, a, ff.norm_weight, cache.ff_prev[li],
+                               shift=ff.shift_tokens)
+        t = F.linear(y, ff.proj_in.weight, ff.proj_in.bias)
+        t = OF.glu_gelu(t) if ff.glu else OF.gelu(t)
+        if ff.sgu is not None:
+            sgu = ff.sgu
+            t = OF.decode_sgu(t, sgu.norm_weight, cache.gate_hist[li],
+                              sgu.spatial_weights, sgu.spatial_biases,
+                              pos_dev)
+            t = F.linear(t, sgu.proj_out.weight, sgu.proj_out.bias)
+        r = F.linear(t, ff.proj_out.weight, ff.proj_out.bias)
+    y = OF.decode_ln_shift(h, r, model.final_norm_weight, None, shift=False)
+    return F.linear(y, model.to_logits.weight, model.to_logits.bias)
+
+
 class GraphedDecodeStep:
     """hipGraph-captured decode step (TODO.md "Serving"; VERDICT r1 item
-    6): one replay = forward_step_static + in-graph pos_dev increment.
+    6): one replay = forward_step_static + in-graph pos_dev increment
+    (``fused=True``: forward_step_fused, the decode kernels).
     The eager per-token step is launch-bound (~500 kernel launches); the
     graph replays them as one unit.
 
@@ -284,9 +333,19 @@ class GraphedDecodeStep:
     """
 
     def __init__(self, model: ProGenBase, cache: DecodeCache,
-                 start_pos: int, warmup: int = 2):
+                 start_pos: int, warmup: int = 2, fused: bool = False):
         dev = next(model.parameters()).device
         batch = cache.attn_prev[0].shape[0]
+        self.seq_len = model.cfg.seq_len
+        if not 0 <= start_pos < self.seq_len:
+            raise IndexError(f"decode start position {start_pos} outside "
+                             f"[0, {self.seq_len})")
+        # host mirror of pos_dev: step() refuses a replay past seq_len
+        # before it is launched (the kernels' own position guard is the
+        # second line of defence)
+        self.next_pos = start_pos
+        self.fused = fused
+        step_fn = forward_step_fused if fused else forward_step_static
         self.cache = cache
         self.token = torch.zeros(batch, dtype=torch.long, device=dev)
         self.pos_dev = torch.tensor(start_pos, dtype=torch.long, device=dev)
@@ -304,15 +363,16 @@ class GraphedDecodeStep:
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
+            # every warmup step runs AT start_pos (the cache is restored
+            # below), so warming up never indexes past seq_len
             for _ in range(warmup):
-                forward_step_static(model, self.token, cache, self.pos_dev)
-                self.pos_dev += 1
+                step_fn(model, self.token, cache, self.pos_dev)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
 
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            self.static_logits = forward_step_static(
+            self.static_logits = step_fn(
                 model, self.token, cache, self.pos_dev)
             self.pos_dev += 1  # in-graph position advance
 
@@ -334,10 +394,30 @@ class GraphedDecodeStep:
     def step(self, tokens: torch.Tensor) -> torch.Tensor:
         """Replay one decode step. ``tokens``: (B,) int64 (host or
         device); returns the (B, V) static logits tensor — copy it out
-        before the next replay."""
+        before the next replay. Raises IndexError, without replaying,
+        once the position has reached seq_len."""
+        if self.next_pos >= self.seq_len:
+            raise IndexError(f"decode past seq_len ({self.seq_len})")
         self.token.copy_(tokens.reshape(-1), non_blocking=False)
         self.graph.replay()
+        self.next_pos += 1
+        self.cache.pos = self.next_pos
         return self.static_logits
+
+
+def _eager_step(model: ProGenBase, token: torch.Tensor, cache: DecodeCache,
+                pos_dev: Optional[torch.Tensor]) -> torch.Tensor:
+    """One uncaptured decode step that advances the cache position.
+    ``pos_dev`` None: ``forward_step``; else ``forward_step_fused`` at the
+    device position ``pos_dev``, which is kept equal to ``cache.pos``."""
+    if pos_dev is None:
+        return forward_step(model, token, cache)
+    if cache.pos >= model.cfg.seq_len:
+        raise IndexError(f"decode past seq_len ({model.cfg.seq_len})")
+    logits = forward_step_fused(model, token, cache, pos_dev)
+    pos_dev += 1
+    cache.pos += 1
+    return logits
 
 
 @torch.no_grad()
@@ -350,13 +430,17 @@ def sample_cached(
     generator: Optional[torch.Generator] = None,
     device=None,
     graph: bool = False,
+    fused: bool = False,
 ) -> torch.Tensor:
     """Drop-in ``utils.sample`` with O(window + n_sgu) per-token cost.
 
     Same decoding semantics (reference: utils.py:106-135): gumbel-max with
     strict-> top-k masking (excluded logits -> 0, not -inf), pad-to-length
     output, everything after the second pad/EOS zeroed. Stops forwarding
-    at EOS instead of emitting to full length."""
+    at EOS instead of emitting to full length.
+
+    ``fused=True`` runs prefill and decode on ``forward_step_fused`` (the
+    decode kernels on a GPU); combinable with ``graph``."""
     dev = next(model.parameters()).device if device is None else device
     # the sequence and sampling math live on CPU (matching utils.sample's
     # generator semantics — its fn closure returns .cpu() logits); only
@@ -369,14 +453,16 @@ def sample_cached(
         start_pos += 1
 
     cache = DecodeCache(model, batch=1, device=dev)
+    pos_dev = torch.zeros((), dtype=torch.long, device=dev) if fused else None
     logits = None
     for p in range(start_pos):                           # prefill
-        logits = forward_step(model, seq[p:p + 1].to(dev), cache)
+        logits = _eager_step(model, seq[p:p + 1].to(dev), cache, pos_dev)
 
     graphed = None
     if graph and dev.type == "cuda":
         logits = logits.clone()  # the static buffer will be reused
-        graphed = GraphedDecodeStep(model, cache, start_pos=start_pos)
+        graphed = GraphedDecodeStep(model, cache, start_pos=start_pos,
+                                    fused=fused)
 
     pads_seen = int((seq[:start_pos] == 0).sum())
     for curr_pos in range(start_pos, length):
@@ -396,9 +482,9 @@ def sample_cached(
             if graphed is not None:
                 logits = graphed.step(seq[curr_pos:curr_pos + 1])
             else:
-                logits = forward_step(model,
-                                      seq[curr_pos:curr_pos + 1].to(dev),
-                                      cache)
+                logits = _eager_step(model,
+                                     seq[curr_pos:curr_pos + 1].to(dev),
+                                     cache, pos_dev)
 
     remove_after_eos = (seq == 0).long().cumsum(dim=-1) > 1
     return seq * (~remove_after_eos).long()
@@ -413,6 +499,7 @@ def sample_cached_batch(
     generator: Optional[torch.Generator] = None,
     device=None,
     graph: bool = False,
+    fused: bool = False,
 ) -> torch.Tensor:
     """Batched incremental decode: one forward_step advances ALL rows
     (the per-layer caches are batch-first), so serving throughput scales
@@ -427,7 +514,8 @@ def sample_cached_batch(
     ``top_k=None`` and ``generator=None`` decoding is greedy argmax and
     each row's output equals its single-row ``sample_cached`` run
     (tests/test_decode.py::test_sample_cached_batch_greedy_parity).
-    """
+    ``fused=True`` steps with ``forward_step_fused``; combinable with
+    ``graph``."""
     dev = next(model.parameters()).device if device is None else device
     primes = [torch.as_tensor(p).long().flatten().cpu() for p in primes]
     B = len(primes)
@@ -437,8 +525,11 @@ def sample_cached_batch(
         seq[i, :lens[i]] = p
 
     cache = DecodeCache(model, batch=B, device=dev)
-    graphed = GraphedDecodeStep(model, cache, start_pos=0) \
+    graphed = GraphedDecodeStep(model, cache, start_pos=0, fused=fused) \
         if (graph and dev.type == "cuda") else None
+    # the graphed step owns its device position; the eager fused one needs one
+    pos_dev = torch.zeros((), dtype=torch.long, device=dev) \
+        if (fused and graphed is None) else None
     greedy = top_k is None and generator is None
     # per-row pad counts over WRITTEN tokens only (the unfilled zero tail
     # must not count as EOS); position 0 is written at entry
@@ -447,7 +538,8 @@ def sample_cached_batch(
         if graphed is not None:
             logits = graphed.step(seq[:, pos])
         else:
-            logits = forward_step(model, seq[:, pos].to(dev), cache)  # (B, V)
+            logits = _eager_step(model, seq[:, pos].to(dev), cache,
+                                 pos_dev)                # (B, V)
         rows = logits.cpu().float()  # no device kernel between replays
         if greedy:
             nxt = rows.argmax(dim=-1)

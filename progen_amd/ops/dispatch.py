@@ -56,6 +56,44 @@ def has_ext() -> bool:
     return _EXT is not None
 
 
+# the decode-step kernels live in a second module (progen_amd._C_decode,
+# ops/hip/decode_bindings.cpp); same policy, loaded on first use
+_EXT_DECODE: Optional[Any] = None
+_EXT_DECODE_ERR: Optional[str] = None
+_TRIED_DECODE = False
+
+
+def _try_load_decode() -> None:
+    global _EXT_DECODE, _EXT_DECODE_ERR, _TRIED_DECODE
+    if _TRIED_DECODE:
+        return
+    _TRIED_DECODE = True
+    try:
+        _EXT_DECODE = importlib.import_module("progen_amd._C_decode")
+    except Exception as e:  # noqa: BLE001 - record and re-raise on GPU use
+        _EXT_DECODE = None
+        _EXT_DECODE_ERR = f"{type(e).__name__}: {e}"
+
+
+def ext_decode() -> Any:
+    """Return the loaded decode-kernel extension, raising loudly if
+    unavailable — the fused decode step never falls back to torch ops."""
+    _try_load_decode()
+    if _EXT_DECODE is None:
+        raise RuntimeError(
+            "progen_amd decode extension (progen_amd._C_decode) is not "
+            f"available (import error: {_EXT_DECODE_ERR}). Build it in-tree "
+            "with `python setup.py build_ext --inplace` "
+            "(PYTORCH_ROCM_ARCH=gfx950)."
+        )
+    return _EXT_DECODE
+
+
+def has_ext_decode() -> bool:
+    _try_load_decode()
+    return _EXT_DECODE is not None
+
+
 def use_hip(t, op: str = None) -> bool:
     """True when tensor t lives on a ROCm GPU (→ HIP kernels are mandatory).
 
@@ -64,7 +102,8 @@ def use_hip(t, op: str = None) -> bool:
     - PROGEN_EAGER_OPS="attn,sgu" routes only the named ops eager —
       the per-kernel bisect lever for the graphed-replay investigation
       (profiles/r02_graphed_nan_investigation.md). Tags: ln, attn, glu,
-      sgu, ce, adamw.
+      sgu, ce, adamw; the fused decode step's ops are dec_ln, dec_attn,
+      dec_sgu.
     """
     if not t.is_cuda:
         return False

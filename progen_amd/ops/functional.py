@@ -304,3 +304,46 @@ def sgu_gate(x: torch.Tensor, norm_weight: torch.Tensor,
             spatial_biases[:n].to(gate_ln.dtype)
         return xa * gate_ln
     return reference.sgu_gate(x, norm_weight, spatial_weights, spatial_biases, eps)
+
+
+# ---------------------------------------------------------------------------
+# fused decode-step ops (inference only; progen_amd._C_decode)
+# ---------------------------------------------------------------------------
+# One row per batch element, caches updated in place, the position read
+# from a 0-dim int64 device tensor — see decode.forward_step_fused. No
+# autograd: the decode step runs under no_grad.
+
+def decode_ln_shift(h: torch.Tensor, res, weight: torch.Tensor, prev,
+                    shift: bool = True, eps: float = 1e-5) -> torch.Tensor:
+    """h <- h + res (in place); y = shift(LN(h) * weight) with the shifted
+    half taken from ``prev``; prev <- LN row (in place). Returns y."""
+    if dispatch.use_hip(h, "dec_ln"):
+        return dispatch.ext_decode().dec_ln_shift(
+            h, res, weight, prev, bool(shift), float(eps))
+    return reference.decode_ln_shift(h, res, weight, prev, shift, eps)
+
+
+def decode_attention(qkv: torch.Tensor, sin: torch.Tensor, cos: torch.Tensor,
+                     pos: torch.Tensor, k_cache: torch.Tensor,
+                     v_cache: torch.Tensor, window_size: int) -> torch.Tensor:
+    """Rotary on q, k and v at row ``pos``, cache write, one attention row
+    over the local band (reference.decode_attention)."""
+    if dispatch.use_hip(qkv, "dec_attn"):
+        return dispatch.ext_decode().dec_attn(
+            qkv, sin, cos, pos, k_cache, v_cache, int(window_size))
+    return reference.decode_attention(qkv, sin, cos, pos, k_cache, v_cache,
+                                      window_size)
+
+
+def decode_sgu(h: torch.Tensor, norm_weight: torch.Tensor,
+               hist: torch.Tensor, spatial_weights: torch.Tensor,
+               spatial_biases: torch.Tensor, pos: torch.Tensor,
+               eps: float = 1e-5) -> torch.Tensor:
+    """Gate LN, history write at row ``pos`` and the causal spatial row of
+    the SGU (reference.decode_sgu)."""
+    if dispatch.use_hip(h, "dec_sgu"):
+        return dispatch.ext_decode().dec_sgu(
+            h, norm_weight, hist, spatial_weights, spatial_biases, pos,
+            float(eps))
+    return reference.decode_sgu(h, norm_weight, hist, spatial_weights,
+                                spatial_biases, pos, eps)

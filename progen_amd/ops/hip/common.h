@@ -98,3 +98,65 @@ __device__ __forceinline__ void gelu_tanh_both(float x, float* val,
   *val = 0.5f * x * (1.0f + t);
   *grad = 0.5f * (1.0f + t) + 0.5f * x * (1.0f - t * t) * dinner;
 }
+
+// 8 consecutive elements as fp32, for kernels instantiated on both storage
+// types: one 16 B load for bf16, two for fp32. ``idx`` is an element index
+// and a multiple of 8, so every access is 16 B aligned.
+template <bool BF>
+__device__ __forceinline__ void ld8(const void* p, long long idx, float* x) {
+  if constexpr (BF) {
+    const bf16x8 v = *(const bf16x8*)((const short*)p + idx);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x[j] = bf2f(v[j]);
+  } else {
+    const f32x4 a = *(const f32x4*)((const float*)p + idx);
+    const f32x4 b = *(const f32x4*)((const float*)p + idx + 4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      x[j] = a[j];
+      x[j + 4] = b[j];
+    }
+  }
+}
+
+template <bool BF>
+__device__ __forceinline__ void st8(void* p, long long idx, const float* x) {
+  if constexpr (BF) {
+    bf16x8 v;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = f2bf(x[j]);
+    *(bf16x8*)((short*)p + idx) = v;
+  } else {
+    f32x4 a, b;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      a[j] = x[j];
+      b[j] = x[j + 4];
+    }
+    *(f32x4*)((float*)p + idx) = a;
+    *(f32x4*)((float*)p + idx + 4) = b;
+  }
+}
+
+// one element of the storage type, and the value an fp32 result takes once
+// it has been stored in that type
+template <bool BF>
+__device__ __forceinline__ float ld1(const void* p, long long idx) {
+  if constexpr (BF) return bf2f(((const short*)p)[idx]);
+  else return ((const float*)p)[idx];
+}
+
+template <bool BF>
+__device__ __forceinline__ float round_trip(float x) {
+  if constexpr (BF) return bf2f(f2bf(x));
+  else return x;
+}
+
+// sum over a 256-thread block, result in every thread. ``red`` holds 4
+// floats of LDS; consecutive calls must use different arrays.
+__device__ __forceinline__ float block256_sum(float v, float* red) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}

@@ -288,3 +288,110 @@ def gumbel_noise(shape, generator=None, device=None, dtype=torch.float32) -> tor
     u = torch.rand(shape, generator=generator, device=device, dtype=dtype)
     eps = 1e-20  # reference: utils.py:20-21 log(t + eps)
     return -torch.log(-torch.log(u + eps) + eps)
+
+
+# ---------------------------------------------------------------------------
+# fused decode-step ops (one row per batch element; ops/hip/decode_*.hip)
+# ---------------------------------------------------------------------------
+# Same signatures and in-place cache effects as the kernels. Tensor indexing
+# only: ``pos`` is a 0-dim int64 tensor and no shape depends on its value,
+# so a step built from these is position-static (decode.forward_step_static).
+# Cache rows a step must not read are dropped with ``where``, never
+# multiplied by zero, so whatever they hold cannot leak into the result.
+
+def decode_ln_shift(
+    h: torch.Tensor,
+    res: Optional[torch.Tensor],
+    g: torch.Tensor,
+    prev: Optional[torch.Tensor],
+    shift: bool,
+    eps: float = 1e-5,
+) -> torch.Tensor:
+    """Residual add + scale-only LN + token shift on (B, D) rows.
+
+    ``h`` becomes h + res in place (rounded to its dtype; the LN reads it
+    as stored). Returns y = [prev[:, :split] | ln[:, split:]] when ``shift``
+    else ln, then ``prev`` becomes ln. ``prev=None`` needs shift=False."""
+    if res is not None:
+        h.add_(res)
+    ln = layernorm_nobias(h, g, eps)
+    if shift:
+        assert prev is not None, "shift needs the previous row"
+        split = -(-h.shape[-1] // 2)
+        y = torch.cat((prev[:, :split], ln[:, split:]), dim=-1)
+    else:
+        y = ln
+    if prev is not None:
+        prev.copy_(ln)
+    return y
+
+
+def decode_attention(
+    qkv: torch.Tensor,
+    rsin: torch.Tensor,
+    rcos: torch.Tensor,
+    pos: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    window: int,
+) -> torch.Tensor:
+    """One local-attention row at position ``pos``.
+
+    qkv: (B, 3*H*dh) unrotated; k_cache/v_cache: (B, H, N, dh), row ``pos``
+    is written with the rotated k and v. Attends over cache rows
+    [max(0, w0 - window), pos], w0 = (pos // window) * window; while
+    pos < window the ``window`` all-zero lookback keys of the full forward
+    enter the softmax unmasked (logit 0, value 0). Returns (B, H*dh)."""
+    B, H, N, dh = k_cache.shape
+    p = pos.reshape(1)
+    sc = rcos.index_select(0, p)[0].to(qkv.dtype)
+    ss = rsin.index_select(0, p)[0].to(qkv.dtype)
+    q, k, v = qkv.view(B, 3, H, dh).unbind(1)
+    q, k, v = (t * sc + rotate_every_two(t) * ss for t in (q, k, v))
+    k_cache.index_copy_(2, p, k.unsqueeze(2))
+    v_cache.index_copy_(2, p, v.unsqueeze(2))
+
+    # fixed 2*window band starting one window before the current one
+    idx = (pos // window) * window - window + \
+        torch.arange(2 * window, device=qkv.device)
+    halo = idx < 0                  # zero lookback keys: logit 0, unmasked
+    live = (idx >= 0) & (idx <= pos)
+    safe = idx.clamp(min=0)
+    zero = torch.zeros((), dtype=qkv.dtype, device=qkv.device)
+    keys = torch.where(live.view(1, 1, -1, 1),
+                       k_cache.index_select(2, safe), zero)
+    vals = torch.where(live.view(1, 1, -1, 1),
+                       v_cache.index_select(2, safe), zero)
+    s = torch.einsum("bhd,bhnd->bhn", q, keys) * (dh ** -0.5)
+    s = s.masked_fill(~(live | halo).view(1, 1, -1), -1e30)
+    s = s - s.amax(dim=-1, keepdim=True)
+    a = s.float().softmax(dim=-1).to(qkv.dtype)
+    return torch.einsum("bhn,bhnd->bhd", a, vals).reshape(B, H * dh)
+
+
+def decode_sgu(
+    h: torch.Tensor,
+    g: torch.Tensor,
+    hist: torch.Tensor,
+    w: torch.Tensor,
+    bias: torch.Tensor,
+    pos: torch.Tensor,
+    eps: float = 1e-5,
+) -> torch.Tensor:
+    """One spatial-gating row at position ``pos``.
+
+    h: (B, 2*d2) = [xa | gate]; hist: (B, N, d2) LN'd gate rows, row ``pos``
+    is written; w: (N, N); bias: (N, 1). Returns
+    xa * (sum_{n <= pos} w[pos, n] * hist[:, n] + bias[pos]), (B, d2)."""
+    p = pos.reshape(1)
+    xa, gate = h.chunk(2, dim=-1)
+    gl = layernorm_nobias(gate, g, eps)
+    hist.index_copy_(1, p, gl.unsqueeze(1))
+    n = hist.shape[1]
+    past = torch.arange(n, device=h.device) <= pos
+    zero = torch.zeros((), dtype=hist.dtype, device=h.device)
+    rows = torch.where(past.view(1, -1, 1), hist, zero)
+    w_row = w.index_select(0, p)[0, :n].to(hist.dtype)
+    gate_out = torch.einsum("n,bnd->bd", w_row, rows) + \
+        bias.index_select(0, p)[0].to(hist.dtype)
+    return xa * gate_out

@@ -28,7 +28,10 @@ load_dotenv()  # reference: sample.py:1-2
 @click.option('--graph', default=False, is_flag=True,
               help='with --cached on GPU: replay the per-token step as one '
                    'captured hipGraph (~2x the eager cached step)')
-def main(seed, checkpoint_path, prime, fast, cached, graph):
+@click.option('--fused', default=False, is_flag=True,
+              help='with --cached: run the step on the fused decode kernels '
+                   '(combinable with --graph)')
+def main(seed, checkpoint_path, prime, fast, cached, graph, fused):
     from progen_amd.tuning import enable_tuned_gemms
     enable_tuned_gemms()
     _, get_last_checkpoint, _ = get_checkpoint_fns(checkpoint_path)
@@ -71,7 +74,8 @@ def main(seed, checkpoint_path, prime, fast, cached, graph):
     if cached:
         from progen_amd.decode import sample_cached
         sampled = sample_cached(module, prime_tensor, seq_len, top_k=25,
-                                add_bos=True, generator=g, graph=graph)
+                                add_bos=True, generator=g, graph=graph,
+                                fused=fused)
     elif fast:
         sampled = sample_fast(fwd, prime_tensor, seq_len, top_k=25,
                               add_bos=True, generator=g,

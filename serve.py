@@ -43,7 +43,8 @@ from progen_amd.utils import load_dotenv
 
 
 def create_app(module: ProGenBase, cfg: ProGenConfig, *,
-               graph: bool = False, meta: Optional[dict] = None):
+               graph: bool = False, fused: bool = False,
+               meta: Optional[dict] = None):
     """Build the FastAPI app around a ready (device-placed, eval) module."""
     from fastapi import FastAPI, HTTPException
     from pydantic import BaseModel
@@ -57,6 +58,7 @@ def create_app(module: ProGenBase, cfg: ProGenConfig, *,
         "seq_len": cfg.seq_len,
         "device": str(device),
         "graph": bool(graph and device.type == "cuda"),
+        "fused": bool(fused),
         **(meta or {}),
     }
 
@@ -100,7 +102,8 @@ def create_app(module: ProGenBase, cfg: ProGenConfig, *,
         t0 = time.perf_counter()
         with lock, torch.no_grad():
             out = sample_cached_batch(module, rows, length, top_k=top_k,
-                                      generator=gen, graph=info["graph"])
+                                      generator=gen, graph=info["graph"],
+                                      fused=info["fused"])
         ms = (time.perf_counter() - t0) * 1e3
         seqs, toks_out = [], []
         for row, prime_row in zip(out, rows):
@@ -143,13 +146,16 @@ def load_module(checkpoint_path: str):
 @click.option("--graph", default=False, is_flag=True,
               help="on GPU: replay the per-token decode step as one "
                    "captured hipGraph (2.1x the eager cached step)")
-def main(checkpoint_path, host, port, graph):
+@click.option("--fused", default=False, is_flag=True,
+              help="run the per-token step on the fused decode kernels "
+                   "(combinable with --graph)")
+def main(checkpoint_path, host, port, graph, fused):
     load_dotenv()
     from progen_amd.tuning import enable_tuned_gemms
     enable_tuned_gemms()
     import uvicorn
     module, cfg, meta = load_module(checkpoint_path)
-    app = create_app(module, cfg, graph=graph, meta=meta)
+    app = create_app(module, cfg, graph=graph, fused=fused, meta=meta)
     uvicorn.run(app, host=host, port=port, log_level="info")
 
 

@@ -1,9 +1,10 @@
-"""In-tree build of the progen_amd._C HIP extension (gfx950 only).
+"""In-tree build of the progen_amd._C and progen_amd._C_decode HIP
+extensions (gfx950 only).
 
     PYTORCH_ROCM_ARCH=gfx950 python setup.py build_ext --inplace
 
-The built .so lands next to the package (progen_amd/_C*.so) so the repo
-snapshot carries it to the GPU box.
+The built .so files land next to the package (progen_amd/_C*.so) so the
+repo snapshot carries them to the GPU box.
 """
 
 import os
@@ -28,17 +29,33 @@ HIP_SOURCES = [
     "progen_amd/ops/hip/colsum.hip",
 ]
 
+# the fused kernels of the cached decode step (progen_amd/decode.py);
+# a module of its own so that progen_amd._C keeps its exact export list
+DECODE_SOURCES = [
+    "progen_amd/ops/hip/decode_bindings.cpp",
+    "progen_amd/ops/hip/decode_ln_shift.hip",
+    "progen_amd/ops/hip/decode_attn.hip",
+    "progen_amd/ops/hip/decode_sgu.hip",
+]
+
+COMPILE_ARGS = {
+    "cxx": ["-O3", "-std=c++17"],
+    "nvcc": ["-O3", "-std=c++17"],
+}
+
 setup(
     name="progen_amd_ext",
     ext_modules=[
         CUDAExtension(
             name="progen_amd._C",
             sources=HIP_SOURCES,
-            extra_compile_args={
-                "cxx": ["-O3", "-std=c++17"],
-                "nvcc": ["-O3", "-std=c++17"],
-            },
-        )
+            extra_compile_args=COMPILE_ARGS,
+        ),
+        CUDAExtension(
+            name="progen_amd._C_decode",
+            sources=DECODE_SOURCES,
+            extra_compile_args=COMPILE_ARGS,
+        ),
     ],
     cmdclass={"build_ext": BuildExtension.with_options(use_ninja=True)},
 )

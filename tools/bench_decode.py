@@ -5,9 +5,10 @@ numbers were mislabeled on a different 2048/24/dh128 model, VERDICT r1
 weak #8).
 
 Modes: eager per-token step, hipGraph-captured step (--graph), batched
-(--batch N). Serving metric: ms/token (batch 1) and tokens/s aggregate.
+(--batch N), fused decode kernels (--fused, with or without --graph).
+Serving metric: ms/token (batch 1) and tokens/s aggregate.
 
-Usage (GPU box):  python tools/bench_decode.py [--tokens 128] [--graph] [--batch 8]
+Usage (GPU box):  python tools/bench_decode.py [--tokens 128] [--graph] [--fused] [--batch 8]
 """
 
 import argparse
@@ -22,7 +23,7 @@ import torch
 from progen_amd import ProGenBase
 from progen_amd.config import ProGenConfig
 from progen_amd.decode import (DecodeCache, GraphedDecodeStep, forward_step,
-                               forward_step_static)
+                               forward_step_fused)
 
 
 def main():
@@ -31,6 +32,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--graph", action="store_true")
     ap.add_argument("--batch", type=int, default=1)
+    ap.add_argument("--fused", action="store_true",
+                    help="step on the fused decode kernels")
     args = ap.parse_args()
 
     # flagship ProGen-1.2B (configs/model/progen_1b.toml)
@@ -52,7 +55,8 @@ def main():
             logits = forward_step(m, tok, cache)
             tok = logits.argmax(dim=-1)
         tok = tok.cpu()
-        g = GraphedDecodeStep(m, cache, start_pos=cache.pos)
+        g = GraphedDecodeStep(m, cache, start_pos=cache.pos,
+                              fused=args.fused)
         # pure-replay rule: sampling runs on the HOST (memcpys only
         # between replays — a device argmax kernel would poison replay)
         for _ in range(args.warmup):
@@ -66,16 +70,27 @@ def main():
         torch.cuda.synchronize()
         mode = "graphed"
     else:
+        if args.fused:
+            pos_dev = torch.zeros((), dtype=torch.long, device="cuda")
+
+            def step(tok):
+                logits = forward_step_fused(m, tok, cache, pos_dev)
+                pos_dev.add_(1)
+                cache.pos += 1
+                return logits
+        else:
+            def step(tok):
+                return forward_step(m, tok, cache)
         for _ in range(args.warmup):
-            logits = forward_step(m, tok, cache)
-            tok = logits.argmax(dim=-1)
+            tok = step(tok).argmax(dim=-1)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.tokens):
-            logits = forward_step(m, tok, cache)
-            tok = logits.argmax(dim=-1)
+            tok = step(tok).argmax(dim=-1)
         torch.cuda.synchronize()
         mode = "eager"
+    if args.fused:
+        mode += "+fused"
     dt = time.perf_counter() - t0
     n = args.tokens * B
     print(f"decode[{mode}, batch {B}]: {args.tokens} steps in {dt:.3f}s -> "
