@@ -5,8 +5,8 @@
 // to(float8): 4 full passes with an fp32 intermediate) eating the
 // entire gain. These kernels make quantization ONE pass each:
 //
-//   quant_e4m3:   bf16 -> e4m3 at a device-scalar scale (v_cvt_pk_fp8
-//                 saturates, so no separate clamp pass);
+//   quant_e4m3:   bf16 -> e4m3 at a device-scalar scale, clamped to
+//                 +-448 in registers (no separate clamp pass);
 //   quant_e4m3_t: (N, K) bf16 row-major -> (K, N) e4m3 row-major
 //                 (the column-major operand torch._scaled_mm needs for
 //                 the dgrad) through 64x64 LDS tiles — both the global
@@ -18,6 +18,14 @@
 
 #define QBLOCK 256
 
+// x / scale clamped to the e4m3 range. On gfx950 v_cvt_pk_fp8_f32 rounds
+// up to 464 to 448 but turns anything larger into the NaN byte 0x7f, so
+// the clamp is not optional: a value beyond 448 * scale (a stale scale)
+// must saturate as clamp(-448, 448).to(float8_e4m3fn) does.
+__device__ __forceinline__ float q_scaled(short b, float inv) {
+  return fminf(fmaxf(bf2f(b) * inv, -448.0f), 448.0f);
+}
+
 __global__ __launch_bounds__(QBLOCK) void quant_e4m3_kernel(
     const short* __restrict__ in, unsigned char* __restrict__ out,
     const float* __restrict__ scale, long long n8) {
@@ -26,16 +34,15 @@ __global__ __launch_bounds__(QBLOCK) void quant_e4m3_kernel(
        i += (long long)gridDim.x * QBLOCK) {
     bf16x8 v = ((const bf16x8*)in)[i];
     unsigned short b01, b23, b45, b67;
-    // v_cvt_pk_fp8_f32 packs two fp32 into two e4m3 bytes, saturating
-    // to +-448 (no inf in e4m3)
+    // v_cvt_pk_fp8_f32 packs two fp32 into two e4m3 bytes (RNE)
     b01 = (unsigned short)__builtin_amdgcn_cvt_pk_fp8_f32(
-        bf2f(((short*)&v)[0]) * inv, bf2f(((short*)&v)[1]) * inv, 0, false);
+        q_scaled(((short*)&v)[0], inv), q_scaled(((short*)&v)[1], inv), 0, false);
     b23 = (unsigned short)__builtin_amdgcn_cvt_pk_fp8_f32(
-        bf2f(((short*)&v)[2]) * inv, bf2f(((short*)&v)[3]) * inv, 0, false);
+        q_scaled(((short*)&v)[2], inv), q_scaled(((short*)&v)[3], inv), 0, false);
     b45 = (unsigned short)__builtin_amdgcn_cvt_pk_fp8_f32(
-        bf2f(((short*)&v)[4]) * inv, bf2f(((short*)&v)[5]) * inv, 0, false);
+        q_scaled(((short*)&v)[4], inv), q_scaled(((short*)&v)[5], inv), 0, false);
     b67 = (unsigned short)__builtin_amdgcn_cvt_pk_fp8_f32(
-        bf2f(((short*)&v)[6]) * inv, bf2f(((short*)&v)[7]) * inv, 0, false);
+        q_scaled(((short*)&v)[6], inv), q_scaled(((short*)&v)[7], inv), 0, false);
     unsigned long long packed = (unsigned long long)b01 |
                                 ((unsigned long long)b23 << 16) |
                                 ((unsigned long long)b45 << 32) |
@@ -67,7 +74,7 @@ __global__ __launch_bounds__(QBLOCK) void quant_e4m3_t_kernel(
       const int r = idx / TT, c = idx % TT;
       const int n = n0 + r, k = k0 + c;
       tile[r][c] = (n < Nr && k < Kc)
-          ? bf2f(in[(long long)n * Kc + k]) * inv : 0.f;
+          ? q_scaled(in[(long long)n * Kc + k], inv) : 0.f;
     }
     __syncthreads();
     // write transposed: out row = k, col = n (coalesced over n)

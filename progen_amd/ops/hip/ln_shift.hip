@@ -46,9 +46,32 @@ __device__ __forceinline__ void ln_block_reduce2(float& a, float& b,
   __syncthreads();
 }
 
+// block-reduce one per-thread partial sum (same scratch, same rules)
+__device__ __forceinline__ float ln_block_reduce1(float a, float* red, int wid,
+                                                  int lane) {
+  a = wave_sum(a);
+  if (lane == 0) red[wid] = a;
+  __syncthreads();
+  if (wid == 0) {
+    float t = (lane < LN_WAVES) ? red[lane] : 0.f;
+#pragma unroll
+    for (int off = LN_WAVES / 2; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
+    if (lane == 0) red[0] = t;
+  }
+  __syncthreads();
+  a = red[0];
+  __syncthreads();
+  return a;
+}
+
 // ---------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------
+// The variance is the CENTRED second moment, mean((x - mu)^2), taken in a
+// second pass once mu is known (as decode_ln_shift.hip and torch do):
+// E[x^2] - mu^2 in fp32 loses (mu/sigma)^2 ulps, 1.5e-5 of rstd at
+// mu = 10 sigma. The fast path re-reads its registers, the slow path the
+// row, so the cost is one more block reduction of the same length.
 
 // RES: fuse the residual add s = x + res (bf16 rounding identical to an
 // eager bf16 add); stats and y are computed on s, and s is written out as
@@ -79,7 +102,7 @@ __global__ __launch_bounds__(LN_BLOCK) void ln_shift_fwd_kernel(
     const int i = threadIdx.x;
     const bool act = i < Dv;
     VEC v;
-    float s = 0.f, ss = 0.f;
+    float s = 0.f;
     if (act) {
       v = x[base + i];
       if (RES) {
@@ -97,15 +120,19 @@ __global__ __launch_bounds__(LN_BLOCK) void ln_shift_fwd_kernel(
         v = sv;
       }
 #pragma unroll
+      for (int j = 0; j < VLEN; ++j)
+        s += IS_BF16 ? bf2f(((short*)&v)[j]) : ((float*)&v)[j];
+    }
+    const float mu = ln_block_reduce1(s, red, wid, lane) / D;
+    float ss = 0.f;
+    if (act) {
+#pragma unroll
       for (int j = 0; j < VLEN; ++j) {
-        float f = IS_BF16 ? bf2f(((short*)&v)[j]) : ((float*)&v)[j];
-        s += f;
-        ss += f * f;
+        float c = (IS_BF16 ? bf2f(((short*)&v)[j]) : ((float*)&v)[j]) - mu;
+        ss += c * c;
       }
     }
-    ln_block_reduce2(s, ss, red, wid, lane);
-    const float mu = s / D;
-    const float var = fmaxf(ss / D - mu * mu, 0.f);
+    const float var = ln_block_reduce1(ss, red, wid, lane) / D;
     const float rs = rsqrtf(var + eps);
     if (threadIdx.x == 0) {
       mean[row] = mu;
@@ -139,7 +166,7 @@ __global__ __launch_bounds__(LN_BLOCK) void ln_shift_fwd_kernel(
     return;
   }
 
-  float s = 0.f, ss = 0.f;
+  float s = 0.f;
   for (int i = threadIdx.x; i < Dv; i += LN_BLOCK) {
     VEC v = x[base + i];
     if (RES) {
@@ -157,16 +184,22 @@ __global__ __launch_bounds__(LN_BLOCK) void ln_shift_fwd_kernel(
       v = sv;
     }
 #pragma unroll
+    for (int j = 0; j < VLEN; ++j)
+      s += IS_BF16 ? bf2f(((short*)&v)[j]) : ((float*)&v)[j];
+  }
+  const float mu = ln_block_reduce1(s, red, wid, lane) / D;
+
+  float ss = 0.f;
+  for (int i = threadIdx.x; i < Dv; i += LN_BLOCK) {
+    // each thread re-reads the vectors it read (with RES: wrote) above
+    VEC v = RES ? s_out[base + i] : x[base + i];
+#pragma unroll
     for (int j = 0; j < VLEN; ++j) {
-      float f = IS_BF16 ? bf2f(((short*)&v)[j]) : ((float*)&v)[j];
-      s += f;
-      ss += f * f;
+      float c = (IS_BF16 ? bf2f(((short*)&v)[j]) : ((float*)&v)[j]) - mu;
+      ss += c * c;
     }
   }
-  ln_block_reduce2(s, ss, red, wid, lane);
-
-  const float mu = s / D;
-  const float var = fmaxf(ss / D - mu * mu, 0.f);
+  const float var = ln_block_reduce1(ss, red, wid, lane) / D;
   const float rs = rsqrtf(var + eps);
   if (threadIdx.x == 0) {
     mean[row] = mu;
