@@ -10,10 +10,31 @@
 //   dS  = P o (dP - D)
 //   dQ' = dS k_s                       (scale folded into staged K^T)
 //   dK' = dS^T q_s                     (scale folded into staged Q^T)
-// followed by attn_bwd_finalize_kernel, which applies the inverse rotary
-// rotation (rotary is linear, so it commutes with accumulation) and
-// casts the fp32 accumulator to bf16 dqkv. Input qkv is PRE-ROTATED
-// (ops/hip/rope_qkv.hip).
+// followed by the inverse rotary rotation (rotary is linear, so it
+// commutes with accumulation) and the cast to bf16 dqkv. Input qkv is
+// PRE-ROTATED (ops/hip/rope_qkv.hip).
+//
+// Two paths, chosen by attn_bwd_launch, bit-identical in dqkv/dhalo:
+//  * fused (attn_bwd_kernel<true>, window <= 256 i.e. one round of
+//    chunks, and enough (batch, head) blocks to fill the chip): grid
+//    (1, H, B); a block walks its windows in ascending order and
+//    finishes everything itself. dQ is rotated and rounded after the
+//    tile loop (bounced through the dead qt/dot LDS regions so that a
+//    row leaves as one 128-B line). A key band's dK/dV come from two
+//    windows — its own and the next one's lookback — and phase 2 gives
+//    a thread the same (key, column) slots in every tile, so the
+//    own-band partial of tile t + wsz/64 in window w and the lookback
+//    partial of tile t in window w+1 belong to the SAME thread: it
+//    parks the former in a thread-private fp32 carry slot (global, but
+//    written and read by that thread alone: no fence, no barrier), and
+//    one window later adds it, rotates with the partner column from
+//    the neighbouring lane, and stores bf16. No dacc/dlook, no second
+//    kernel: the 4 GB/call fp32 round trip of the other path is gone
+//    (profiles/attn_bwd_fused_finalize.md).
+//  * two kernels (attn_bwd_kernel<false> + attn_bwd_finalize_kernel,
+//    every other shape): one block per (batch, head, window) stores
+//    fp32 partials, finalize sums own + lookback, rotates and rounds.
+// What follows describes the per-window body, which both share.
 //
 // Geometry: block = one (batch, head, window), EIGHT waves of 32-row
 // q-chunks (round-2 ladder, tools/ablate_attn_bwd.hip: the V4 2-barrier
@@ -40,12 +61,14 @@
 //   tile (an earlier ks-half split needed an LDS partial combine and
 //   four barriers; PMC showed 53% of cycles parked on them).
 // Every dV/dK element is produced by exactly ONE wave, so the stores
-// are PLAIN (no atomics): each window's own-band gradients go to dacc,
-// its lookback-band gradients to a separate dlook buffer, and
-// attn_bwd_finalize_kernel sums the two (adjacent windows share keys
-// through the lookback, progen.py:90-91). dQ rows are exclusively
-// owned -> plain fp32 stores. Window 0's lookback keys are the zero
-// pad; their gradients are discarded.
+// are PLAIN (no atomics): on the two-kernel path each window's own-band
+// gradients go to dacc, its lookback-band gradients to a separate dlook
+// buffer, and attn_bwd_finalize_kernel sums the two (adjacent windows
+// share keys through the lookback, progen.py:90-91); the fused path
+// sums the same two operands in the thread that produced both. dQ rows
+// are exclusively owned -> plain stores. Window 0's lookback keys are
+// the zero pad; their gradients are discarded (or, with a CP halo,
+// stored fp32 and still rotated to dhalo — on both paths).
 //
 // MFMA operand LDS images (XOR-swizzled, byte ^= (row&7)<<4 except ds2):
 //   k_lds  [key][dh]   k'           (S B-fragments)
@@ -96,6 +119,42 @@ typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 bf16x4t;
 #define V5_WAVES 8
 #define V5_BLOCK (V5_WAVES * WAVE)
 
+// One element of the inverse rotary rotation, rounded to bf16:
+//   dx[2i]   = dy[2i] c + dy[2i+1] s     (self = dy[2i],   s_signed = +s)
+//   dx[2i+1] = dy[2i+1] c - dy[2i] s     (self = dy[2i+1], s_signed = -s)
+// The fused epilogues and attn_bwd_finalize_kernel both go through it,
+// with the operation order spelled out, so that the compiler cannot
+// contract the two paths differently and their dqkv agree bit for bit.
+// The order — round partner*s, then one fma on self*c — is the one the
+// compiler had picked for finalize when it was free to choose, so dqkv
+// is also what it was before this helper existed.
+__device__ __forceinline__ short inv_rot_bf16(float self, float partner,
+                                              float c, float s_signed) {
+  return f2bf(__fmaf_rn(self, c, __fmul_rn(partner, s_signed)));
+}
+
+// dK/dV store shape of the fused path. 1: lane pairs trade values so
+// that the even lane holds keys r = 0, 1 and the odd lane r = 2, 3 of
+// both columns of a rotation pair, and each stores bf16 PAIRS (8 dword
+// stores per thread and tile). 0: every lane stores its own 16 bf16
+// singly. Timings of both: profiles/attn_bwd_fused_finalize.md.
+#ifndef ATTN_BWD_PACKED_STORE
+#define ATTN_BWD_PACKED_STORE 1
+#endif
+#if ATTN_BWD_PACKED_STORE
+constexpr int kEpiR = 2;   // keys per lane whose sin/cos the epilogue needs
+__device__ __forceinline__ int epi_r(int e, int l15) { return e + 2 * (l15 & 1); }
+#else
+constexpr int kEpiR = 4;
+__device__ __forceinline__ int epi_r(int e, int) { return e; }
+#endif
+
+// FUSED = false: one block per (window, head, batch), fp32 partials to
+// dacc/dlook for attn_bwd_finalize_kernel. FUSED = true: one block per
+// (head, batch) walks its windows in ascending order and writes bf16
+// dqkv itself (rounds == 1 only); dacc/dlook are unused, carry/rsin/
+// rcos/dqkv are used instead.
+template <bool FUSED>
 __global__ __launch_bounds__(V5_BLOCK) void attn_bwd_kernel(
     const short* __restrict__ dout, const short* __restrict__ qkv,
     const short* __restrict__ halo,   // CP lookback for window 0 (see
@@ -104,13 +163,21 @@ __global__ __launch_bounds__(V5_BLOCK) void attn_bwd_kernel(
     float* __restrict__ dacc, float* __restrict__ dlook,
     float* __restrict__ dhalo,        // (B, wsz, 2*H*DH) fp32 window-0
                                       // lookback grads (CP) or nullptr
-    int B, int N, int H, int wsz) {
-  const int window = blockIdx.x;
+    const float* __restrict__ rsin, const float* __restrict__ rcos,
+    float* carry,                     // (B*H, wsz/64, 2, 2, 512) f32x4
+    short* __restrict__ dqkv, int B, int N, int H, int wsz) {
+  const int nwin = N / wsz;
+  const int w_begin = FUSED ? 0 : (int)blockIdx.x;
+  const int w_end = FUSED ? nwin : w_begin + 1;
   const int head = blockIdx.y;
   const int batch = blockIdx.z;
 
-  const int lane = threadIdx.x % WAVE;
-  const int wid = threadIdx.x / WAVE;   // 0..7
+  // (the per-window body keeps its indentation: it is the two-kernel
+  // path's whole kernel, run once there and N/wsz times here)
+  for (int window = w_begin; window < w_end; ++window) {
+  const int tid = threadIdx.x;
+  const int lane = tid % WAVE;
+  const int wid = tid / WAVE;           // 0..7
   const int l15 = lane & 15;
   const int l4 = lane >> 4;
   const int pid = wid >> 1;             // pair region 0..3
@@ -152,8 +219,8 @@ __global__ __launch_bounds__(V5_BLOCK) void attn_bwd_kernel(
   const int rounds = (chunks64 + 3) / 4;
 
   // block-wide k/v tile staging: 512 threads cover 64 keys x 64 dh
-  const int su_key = (int)threadIdx.x >> 3;
-  const int su_d0 = ((int)threadIdx.x & 7) * 8;
+  const int su_key = tid >> 3;
+  const int su_d0 = (tid & 7) * 8;
 
   for (int round = 0; round < rounds; ++round) {
     const int c64 = round * 4 + pid;             // this pair's 64-chunk
@@ -171,6 +238,18 @@ __global__ __launch_bounds__(V5_BLOCK) void attn_bwd_kernel(
       for (int d = 0; d < 4; ++d) dqacc[m][d] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     if (active) {
+      // fused: the prologue's ids come from an opaque copy of the thread
+      // id (see the dQ epilogue), so that its addresses are formed here,
+      // once per window, and not held across the previous tile loop
+      int ptid = tid;
+      if constexpr (FUSED) asm volatile("" : "+v"(ptid));
+      const int lane = ptid % WAVE, l15 = lane & 15, l4 = lane >> 4;
+      const int ppid = ptid / WAVE >> 1, colbase = (ptid / WAVE & 1) * 32;
+      const int q0 = window * wsz + (round * 4 + ppid) * 64 + colbase;
+      char* qt_lds = qt_base + ppid * 8192;
+      char* dot_lds = dot_base + ppid * 8192;
+      float* d_lds = d_base + ppid * 64;
+      float* lse_lds = lse_base + ppid * 64;
 #pragma unroll
       for (int m = 0; m < 2; ++m) {
         const int row = q0 + m * 16 + l15;
@@ -411,6 +490,48 @@ __global__ __launch_bounds__(V5_BLOCK) void attn_bwd_kernel(
           dv[n] = (f32x4){0.f, 0.f, 0.f, 0.f};
           dk[n] = (f32x4){0.f, 0.f, 0.f, 0.f};
         }
+        const bool lookback = kb < wsz;
+        // fused epilogue operands, requested before the MFMA loop so
+        // their latency hides under it. ``fin``: this tile's values are
+        // final after the optional carry add (lookback tiles of window
+        // >= 1, own tiles of the last window); otherwise own tiles park
+        // in the carry and window 0's lookback goes the dhalo way.
+        const bool fin = FUSED && (lookback ? window > 0 : window == nwin - 1);
+        const bool add = FUSED && lookback && window > 0;
+        // addresses: a block-uniform base plus a 32-bit per-thread
+        // offset, so that nothing 64-bit per thread stays live through
+        // phase 1
+        const int kt0 = (window - 1) * wsz + kb;          // tile's first key
+        const int keyq = (wid & 3) * 16 + l4 * 4;         // thread's 4 keys
+        const int dcol0 = dh0 * 16 + l15;
+        f32x4* cbase = nullptr;
+        f32x4 cin[2][2];                 // [n][k|v]
+        float esin[2][kEpiR], ecos[2][kEpiR];
+        if constexpr (FUSED) {
+          const int ctile = lookback ? t : t - chunks64;
+          cbase = (f32x4*)carry +
+                  (((long long)batch * H + head) * chunks64 + ctile) * 2048;
+          if (add) {
+#pragma unroll
+            for (int n = 0; n < 2; ++n)
+#pragma unroll
+              for (int kv = 0; kv < 2; ++kv)
+                cin[n][kv] = cbase[(n * 2 + kv) * 512 + tid];
+          }
+          if (fin) {
+            const float* ts = rsin + (long long)kt0 * DH;
+            const float* tc = rcos + (long long)kt0 * DH;
+#pragma unroll
+            for (int n = 0; n < 2; ++n)
+#pragma unroll
+              for (int e = 0; e < kEpiR; ++e) {
+                const int ti = (keyq + epi_r(e, l15)) * DH +
+                               ((dcol0 + n * 16) & ~1);
+                esin[n][e] = ts[ti];
+                ecos[n][e] = tc[ti];
+              }
+          }
+        }
         __builtin_amdgcn_s_setprio(1);
         for (int c = c_min; c < nactive; ++c) {
           char* pds_c = pds_base + c * 8192;
@@ -437,7 +558,66 @@ __global__ __launch_bounds__(V5_BLOCK) void attn_bwd_kernel(
           }
         }
         __builtin_amdgcn_s_setprio(0);
-        const bool lookback = kb < wsz;
+        if (fin) {
+          // final values: own + lookback (the two operands finalize
+          // adds), inverse rotation with the partner column from the
+          // neighbouring lane, bf16 straight into dqkv
+#pragma unroll
+          for (int n = 0; n < 2; ++n) {
+            if (add) {
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                ((float*)&dk[n])[r] =
+                    __fadd_rn(((float*)&cin[n][0])[r], ((float*)&dk[n])[r]);
+                ((float*)&dv[n])[r] =
+                    __fadd_rn(((float*)&cin[n][1])[r], ((float*)&dv[n])[r]);
+              }
+            }
+            const bool odd = l15 & 1;
+            const int hd3 = 3 * H * DH;
+#pragma unroll
+            for (int kv = 0; kv < 2; ++kv) {
+              const float* y = kv ? (const float*)&dv[n] : (const float*)&dk[n];
+              short* dst = dqkv + qkv_bn + (long long)kt0 * HD3 +
+                           (kv ? v_off : k_off);
+              const int col = dcol0 + n * 16;
+#if ATTN_BWD_PACKED_STORE
+              // even lane: keys r = 0, 1; odd lane: r = 2, 3; each
+              // stores the (even, odd) column pair as one dword
+#pragma unroll
+              for (int e = 0; e < 2; ++e) {
+                const float a = y[e], b = y[e + 2];
+                const float recv = __shfl_xor(odd ? a : b, 1, 64);
+                const float y0 = odd ? recv : a;
+                const float y1 = odd ? b : recv;
+                const unsigned lo = (unsigned short)inv_rot_bf16(
+                    y0, y1, ecos[n][e], esin[n][e]);
+                const unsigned hi = (unsigned short)inv_rot_bf16(
+                    y1, y0, ecos[n][e], -esin[n][e]);
+                *(unsigned*)(dst + (keyq + epi_r(e, l15)) * hd3 + (col & ~1)) =
+                    lo | (hi << 16);
+              }
+#else
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                const float other = __shfl_xor(y[r], 1, 64);
+                dst[(keyq + r) * hd3 + col] =
+                    inv_rot_bf16(y[r], other, ecos[n][r],
+                                 odd ? -esin[n][r] : esin[n][r]);
+              }
+#endif
+            }
+          }
+        } else if (FUSED && !lookback) {
+          // own band of a window that has a successor: park the fp32
+          // partials in this thread's carry slot; the same thread adds
+          // them at the lookback tile t - wsz/64 of the next window
+#pragma unroll
+          for (int n = 0; n < 2; ++n) {
+            cbase[(n * 2 + 0) * 512 + tid] = dk[n];
+            cbase[(n * 2 + 1) * 512 + tid] = dv[n];
+          }
+        } else {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int kpos = (window - 1) * wsz + kb + (wid & 3) * 16 + l4 * 4 + r;
@@ -471,11 +651,63 @@ __global__ __launch_bounds__(V5_BLOCK) void attn_bwd_kernel(
             dstk[dcol] = vk;
           }
         }
+        }
       }
       __syncthreads();  // barrier B: slices done before t+1's phase 1
     }
 
-    if (active) {
+    if (FUSED && active) {
+      // dQ rows are this wave's alone. Bounce them through the (dead
+      // after the last barrier B) qt / dot pair regions — lower wave
+      // half in qt, upper in dot, 32 rows x 256 B each, 64-B granules
+      // XORed by l4 so the four row groups of a store miss each other's
+      // banks — so that every lane rotates 8 consecutive channels of a
+      // row the way finalize does and a row leaves as one 128-B line.
+      // Lane and wave ids come from a thread id the optimiser cannot
+      // see through: it would otherwise form this epilogue's addresses
+      // before the tile loop and, with phase 1 at 244 VGPRs, spill them.
+      int etid = threadIdx.x;
+      asm volatile("" : "+v"(etid));
+      const int elane = etid % WAVE, ewid = etid / WAVE;
+      const int el15 = elane & 15, el4 = elane >> 4;
+      char* bounce = ((ewid & 1) ? dot_base : qt_base) + (ewid >> 1) * 8192;
+      const int eq0 = window * wsz + (ewid >> 1) * 64 + (ewid & 1) * 32;
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int brow = m * 16 + el4 * 4 + r;
+#pragma unroll
+          for (int n = 0; n < 4; ++n)
+            *(float*)(bounce + brow * 256 +
+                      (((n * 16 + el15) * 4) ^ (el4 << 6))) =
+                ((float*)&dqacc[m][n])[r];
+        }
+      // same-wave DS ordering is program order: no barrier
+      const short* dq_w = dqkv + qkv_bn + (long long)eq0 * HD3 + q_off;
+      const float* sin_w = rsin + (long long)eq0 * DH;
+      const float* cos_w = rcos + (long long)eq0 * DH;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int brow = i * 8 + (elane >> 3);
+        const int d0 = (elane & 7) * 8;
+        const int boff = brow * 256 + ((d0 * 4) ^ (((brow >> 2) & 3) << 6));
+        float x[8], sv[8], cv[8];
+        *(f32x4*)(x) = *(const f32x4*)(bounce + boff);
+        *(f32x4*)(x + 4) = *(const f32x4*)(bounce + boff + 16);
+        load_rope(sin_w, cos_w, brow, d0, sv, cv);
+        bf16x8 o;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+          ((short*)&o)[2 * p] =
+              inv_rot_bf16(x[2 * p], x[2 * p + 1], cv[2 * p], sv[2 * p]);
+          ((short*)&o)[2 * p + 1] =
+              inv_rot_bf16(x[2 * p + 1], x[2 * p], cv[2 * p], -sv[2 * p]);
+        }
+        *(bf16x8*)((short*)dq_w + brow * (3 * H * DH) + d0) = o;
+      }
+    }
+    if (!FUSED && active) {
 #pragma unroll
       for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -489,10 +721,12 @@ __global__ __launch_bounds__(V5_BLOCK) void attn_bwd_kernel(
     }
     __syncthreads();
   }
+  }  // window
 }
 
 // ---------------------------------------------------------------------------
 // finalize: inverse rotary rotation on the fp32 accumulator -> bf16 dqkv
+// (two-kernel path)
 // ---------------------------------------------------------------------------
 
 __global__ __launch_bounds__(256) void attn_bwd_finalize_kernel(
@@ -522,37 +756,61 @@ __global__ __launch_bounds__(256) void attn_bwd_finalize_kernel(
     if (hslot >= H && (n / wsz) < (N / wsz) - 1) {
       const long long loff = bn * HD2 + (long long)(hslot - H) * DH + d0;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) x[j] += dlook[loff + j];
+      for (int j = 0; j < 8; ++j) x[j] = __fadd_rn(x[j], dlook[loff + j]);
     }
     load_rope(rsin, rcos, n, d0, sv, cv);
-    // inverse rotation: dx[2i] = dy[2i] c + dy[2i+1] s;
-    //                   dx[2i+1] = dy[2i+1] c - dy[2i] s
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      float y0 = x[2 * p], y1 = x[2 * p + 1];
-      float s = sv[2 * p], c = cv[2 * p];
-      x[2 * p] = y0 * c + y1 * s;
-      x[2 * p + 1] = y1 * c - y0 * s;
-    }
     bf16x8 o;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) ((short*)&o)[j] = f2bf(x[j]);
+    for (int p = 0; p < 4; ++p) {
+      ((short*)&o)[2 * p] =
+          inv_rot_bf16(x[2 * p], x[2 * p + 1], cv[2 * p], sv[2 * p]);
+      ((short*)&o)[2 * p + 1] =
+          inv_rot_bf16(x[2 * p + 1], x[2 * p], cv[2 * p], -sv[2 * p]);
+    }
     *(bf16x8*)(dqkv + off) = o;
   }
 }
 
+// Fused-path rule. The fused kernel needs rounds == 1 (window <= 256).
+// Its grid is (1, H, B): N/wsz times fewer blocks, each N/wsz times as
+// long, so it pays only once H*B blocks fill the chip; the threshold is
+// the smallest measured H*B at which it was not slower than the two
+// kernels (profiles/attn_bwd_fused_finalize.md).
+#define ATTN_BWD_FUSED_MIN_HB 1536
+
 extern "C" {
 
+int attn_bwd_fused_supported(int wsz) { return wsz <= 4 * 64; }
+
+int attn_bwd_pick_fused(int B, int N, int H, int wsz) {
+  (void)N;
+  return attn_bwd_fused_supported(wsz) &&
+         (long long)H * B >= ATTN_BWD_FUSED_MIN_HB;
+}
+
+// fused != 0: dacc/dlook are unused (may be null) and ``carry`` holds
+// B*H*wsz*128 floats; fused == 0: ``carry`` is unused.
 hipError_t attn_bwd_launch(const void* dout, const void* qkv, const void* halo,
                            const float* rsin, const float* rcos,
                            const void* out, const float* lse, float* dacc,
-                           float* dlook, float* dhalo, void* dqkv, int B, int N,
-                           int H, int wsz, hipStream_t stream) {
-  dim3 grid(N / wsz, H, B), block(V5_BLOCK);  // 8 waves: 2/SIMD
+                           float* dlook, float* dhalo, float* carry,
+                           void* dqkv, int B, int N, int H, int wsz, int fused,
+                           hipStream_t stream) {
+  dim3 block(V5_BLOCK);  // 8 waves: 2/SIMD
   size_t lds = 24576 + 131072 + 2048;  // 154 KiB
-  attn_bwd_kernel<<<grid, block, lds, stream>>>(
+  if (fused) {
+    if (!attn_bwd_fused_supported(wsz)) return hipErrorInvalidValue;
+    attn_bwd_kernel<true><<<dim3(1, H, B), block, lds, stream>>>(
+        (const short*)dout, (const short*)qkv, (const short*)halo,
+        (const short*)out, lse, nullptr, nullptr, dhalo, rsin, rcos, carry,
+        (short*)dqkv, B, N, H, wsz);
+    return hipGetLastError();
+  }
+  dim3 grid(N / wsz, H, B);
+  attn_bwd_kernel<false><<<grid, block, lds, stream>>>(
       (const short*)dout, (const short*)qkv, (const short*)halo,
-      (const short*)out, lse, dacc, dlook, dhalo, B, N, H, wsz);
+      (const short*)out, lse, dacc, dlook, dhalo, nullptr, nullptr, nullptr,
+      nullptr, B, N, H, wsz);
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return err;
   int gx = (3 * H * (DH / 8) + 255) / 256;

@@ -409,7 +409,8 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& qkv,
                                  const at::Tensor& rcos, const at::Tensor& out,
                                  const at::Tensor& lse, int64_t heads,
                                  int64_t window,
-                                 const c10::optional<at::Tensor>& halo) {
+                                 const c10::optional<at::Tensor>& halo,
+                                 c10::optional<bool> fused) {
   const char* op = "attn_bwd";
   const int H = extent_int(op, "heads", heads, kGridYZ);
   const int wsz = extent_int(op, "window", window);
@@ -439,12 +440,25 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& qkv,
                 ARG(rcos)});
   if (halo) same_gpu(op, {ARG(qkv), Arg{"halo", *halo}});
 
+  // fused = None: the launcher's rule picks the path
+  CHK(!(fused && *fused) || attn_bwd_fused_supported(wsz), op, "fused=True",
+      window, "must have window <= 256 (a single round of chunks)");
+  const bool use_fused =
+      fused ? *fused : attn_bwd_pick_fused(Bi, Ni, H, wsz) != 0;
+
   DeviceScope dev(qkv);
   // plain-store accumulators: every element is written (dq by its row
-  // owner; own/lookback k,v by their single writing block) -> no zeroing
+  // owner; own/lookback k,v by their single writing block) -> no zeroing.
+  // The fused path keeps them on chip: all it needs is its per-block
+  // carry of one window's own-band dK/dV, written before it is read.
   const auto f32 = qkv.options().dtype(at::kFloat);
-  auto dacc = at::empty_like(qkv, f32);
-  auto dlook = at::empty({B, N, 2 * heads * 64}, f32);
+  at::Tensor dacc, dlook, carry;
+  if (use_fused) {
+    carry = at::empty({B * heads * window * 128}, f32);
+  } else {
+    dacc = at::empty_like(qkv, f32);
+    dlook = at::empty({B, N, 2 * heads * 64}, f32);
+  }
   auto dqkv = at::empty_like(qkv);
   // window-0 slices write every element of their bands (plain stores), so
   // no zeroing needed here either
@@ -454,11 +468,25 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& qkv,
                  dout.data_ptr(), qkv.data_ptr(),
                  halo ? halo->data_ptr() : nullptr, rsin.data_ptr<float>(),
                  rcos.data_ptr<float>(), out.data_ptr(), lse.data_ptr<float>(),
-                 dacc.data_ptr<float>(), dlook.data_ptr<float>(),
-                 halo ? dhalo.data_ptr<float>() : nullptr, dqkv.data_ptr(), Bi,
-                 Ni, H, wsz, dev.stream));
+                 use_fused ? nullptr : dacc.data_ptr<float>(),
+                 use_fused ? nullptr : dlook.data_ptr<float>(),
+                 halo ? dhalo.data_ptr<float>() : nullptr,
+                 use_fused ? carry.data_ptr<float>() : nullptr,
+                 dqkv.data_ptr(), Bi, Ni, H, wsz, use_fused ? 1 : 0,
+                 dev.stream));
   if (halo) return {dqkv, dhalo};
   return {dqkv};
+}
+
+// which path attn_bwd takes at this shape when ``fused`` is left None
+std::string attn_bwd_path(int64_t B, int64_t N, int64_t heads,
+                          int64_t window) {
+  const char* op = "_attn_bwd_path";
+  const int H = extent_int(op, "heads", heads, kGridYZ);
+  const int wsz = extent_int(op, "window", window);
+  const int Bi = extent_int(op, "B", B, kGridYZ);
+  const int Ni = extent_int(op, "N", N);
+  return attn_bwd_pick_fused(Bi, Ni, H, wsz) ? "fused" : "two_kernel";
 }
 
 // ---------------------------------------------------------------------------
@@ -688,7 +716,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_bwd", &attn_bwd, "fused local attention backward",
         py::arg("dout"), py::arg("qkv"), py::arg("rsin"), py::arg("rcos"),
         py::arg("out"), py::arg("lse"), py::arg("heads"), py::arg("window"),
-        py::arg("halo") = py::none());
+        py::arg("halo") = py::none(), py::arg("fused") = py::none());
+  // underscore: a query, not a kernel entry point
+  m.def("_attn_bwd_path", &attn_bwd_path,
+        "path attn_bwd picks when fused is None: 'fused' or 'two_kernel'",
+        py::arg("B"), py::arg("N"), py::arg("heads"), py::arg("window"));
   m.def("crc32c", &crc32c_host, "CRC-32C (slicing-by-8, host)");
   m.def("colsum", &colsum, "bf16 column sum (bias grads), fp32 accum");
   m.def("fp8_quantize", &fp8_quantize, "fused bf16 -> e4m3 at device scale");

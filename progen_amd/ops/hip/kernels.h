@@ -61,8 +61,13 @@ hipError_t attn_fwd_launch(const void* qkv_rot, const void* halo, void* out,
 hipError_t attn_bwd_launch(const void* dout, const void* qkv, const void* halo,
                            const float* rsin, const float* rcos,
                            const void* out, const float* lse, float* dacc,
-                           float* dlook, float* dhalo, void* dqkv, int B, int N,
-                           int H, int wsz, hipStream_t stream);
+                           float* dlook, float* dhalo, float* carry,
+                           void* dqkv, int B, int N, int H, int wsz, int fused,
+                           hipStream_t stream);
+// the fused single-kernel path: whether it exists for this window, and
+// whether the launcher's rule takes it when the caller does not say
+int attn_bwd_fused_supported(int wsz);
+int attn_bwd_pick_fused(int B, int N, int H, int wsz);
 
 hipError_t sgu_fwd_launch(const void* xa, const void* g_ln, const void* w,
                           const float* bias, void* out, void* gate_out, int B,
