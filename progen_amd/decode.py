@@ -266,7 +266,8 @@ def forward_step_static(model: ProGenBase, token: torch.Tensor,
 @torch.no_grad()
 def forward_step_fused(model: ProGenBase, token: torch.Tensor,
                        cache: DecodeCache,
-                       pos_dev: torch.Tensor) -> torch.Tensor:
+                       pos_dev: torch.Tensor,
+                       fused_linear: bool = False) -> torch.Tensor:
     """Decode step on the fused decode kernels: same contract as
     ``forward_step_static`` (position from the 0-dim int64 ``pos_dev``,
     same ``DecodeCache``, position NOT advanced), but every non-GEMM op of
@@ -278,8 +279,23 @@ def forward_step_fused(model: ProGenBase, token: torch.Tensor,
     The branch output is carried into the next ``decode_ln_shift`` as its
     residual, as in ``ProGenBase.forward``; the final norm consumes the
     last one. No workgroup of any kernel waits on another, so the step is
-    as capturable and replayable as the static one."""
+    as capturable and replayable as the static one.
+
+    ``fused_linear=True`` sends the six projections and the logits head
+    through ``OF.decode_linear`` (ops/hip/decode_linear.hip on a GPU), with
+    the bias and the GLU/GELU of ``proj_in`` folded in: 7 launches per GLU
+    layer and 9 per SGU layer, and no bias copy. On the CPU it computes
+    the same ops as the default, bit for bit."""
     cfg = model.cfg
+    if fused_linear:
+        def linear(x, lin, act="none"):
+            return OF.decode_linear(x, lin.weight, lin.bias, act)
+    else:
+        def linear(x, lin, act="none"):
+            y = F.linear(x, lin.weight, lin.bias)
+            if act == "glu":
+                return OF.glu_gelu(y)
+            return OF.gelu(y) if act == "gelu" else y
     if model.rotary_sin.dtype != torch.float32:
         sin, cos = R.fixed_pos_embedding(cfg.seq_len, cfg.dim_head,
                                          device=model.rotary_sin.device)
@@ -290,30 +306,31 @@ def forward_step_fused(model: ProGenBase, token: torch.Tensor,
     for li, (attn, ff) in enumerate(model.layers):
         y = OF.decode_ln_shift(h, r, attn.norm_weight, cache.attn_prev[li],
                                shift=attn.shift_tokens)
-        qkv = F.linear(y, attn.to_qkv.weight)
+        qkv = linear(y, attn.to_qkv)
         out = OF.decode_attention(qkv, sin, cos, pos_dev, cache.k[li],
                                   cache.v[li], attn.window_size)
-        a = F.linear(out, attn.to_out.weight, attn.to_out.bias)
+        a = linear(out, attn.to_out)
 
         y = OF.decode_ln_shift(h, a, ff.norm_weight, cache.ff_prev[li],
                                shift=ff.shift_tokens)
-        t = F.linear(y, ff.proj_in.weight, ff.proj_in.bias)
-        t = OF.glu_gelu(t) if ff.glu else OF.gelu(t)
+        t = linear(y, ff.proj_in, "glu" if ff.glu else "gelu")
         if ff.sgu is not None:
             sgu = ff.sgu
             t = OF.decode_sgu(t, sgu.norm_weight, cache.gate_hist[li],
                               sgu.spatial_weights, sgu.spatial_biases,
                               pos_dev)
-            t = F.linear(t, sgu.proj_out.weight, sgu.proj_out.bias)
-        r = F.linear(t, ff.proj_out.weight, ff.proj_out.bias)
+            t = linear(t, sgu.proj_out)
+        r = linear(t, ff.proj_out)
     y = OF.decode_ln_shift(h, r, model.final_norm_weight, None, shift=False)
-    return F.linear(y, model.to_logits.weight, model.to_logits.bias)
+    return linear(y, model.to_logits)
 
 
 class GraphedDecodeStep:
     """hipGraph-captured decode step (TODO.md "Serving"; VERDICT r1 item
     6): one replay = forward_step_static + in-graph pos_dev increment
-    (``fused=True``: forward_step_fused, the decode kernels).
+    (``fused=True``: forward_step_fused, the decode kernels;
+    ``fused_linear=True`` on top of it: its projections on the decode
+    linear kernel).
     The eager per-token step is launch-bound (~500 kernel launches); the
     graph replays them as one unit.
 
@@ -333,7 +350,9 @@ class GraphedDecodeStep:
     """
 
     def __init__(self, model: ProGenBase, cache: DecodeCache,
-                 start_pos: int, warmup: int = 2, fused: bool = False):
+                 start_pos: int, warmup: int = 2, fused: bool = False,
+                 fused_linear: bool = False):
+        _check_fused_linear(fused, fused_linear)
         dev = next(model.parameters()).device
         batch = cache.attn_prev[0].shape[0]
         self.seq_len = model.cfg.seq_len
@@ -345,7 +364,13 @@ class GraphedDecodeStep:
         # second line of defence)
         self.next_pos = start_pos
         self.fused = fused
-        step_fn = forward_step_fused if fused else forward_step_static
+        self.fused_linear = fused_linear
+        if fused:
+            def step_fn(model, token, cache, pos_dev):
+                return forward_step_fused(model, token, cache, pos_dev,
+                                          fused_linear=fused_linear)
+        else:
+            step_fn = forward_step_static
         self.cache = cache
         self.token = torch.zeros(batch, dtype=torch.long, device=dev)
         self.pos_dev = torch.tensor(start_pos, dtype=torch.long, device=dev)
@@ -405,8 +430,15 @@ class GraphedDecodeStep:
         return self.static_logits
 
 
+def _check_fused_linear(fused: bool, fused_linear: bool) -> None:
+    if fused_linear and not fused:
+        raise ValueError("fused_linear=True needs fused=True: the decode "
+                         "linear kernel is part of the fused decode step")
+
+
 def _eager_step(model: ProGenBase, token: torch.Tensor, cache: DecodeCache,
-                pos_dev: Optional[torch.Tensor]) -> torch.Tensor:
+                pos_dev: Optional[torch.Tensor],
+                fused_linear: bool = False) -> torch.Tensor:
     """One uncaptured decode step that advances the cache position.
     ``pos_dev`` None: ``forward_step``; else ``forward_step_fused`` at the
     device position ``pos_dev``, which is kept equal to ``cache.pos``."""
@@ -414,7 +446,8 @@ def _eager_step(model: ProGenBase, token: torch.Tensor, cache: DecodeCache,
         return forward_step(model, token, cache)
     if cache.pos >= model.cfg.seq_len:
         raise IndexError(f"decode past seq_len ({model.cfg.seq_len})")
-    logits = forward_step_fused(model, token, cache, pos_dev)
+    logits = forward_step_fused(model, token, cache, pos_dev,
+                                fused_linear=fused_linear)
     pos_dev += 1
     cache.pos += 1
     return logits
@@ -431,6 +464,7 @@ def sample_cached(
     device=None,
     graph: bool = False,
     fused: bool = False,
+    fused_linear: bool = False,
 ) -> torch.Tensor:
     """Drop-in ``utils.sample`` with O(window + n_sgu) per-token cost.
 
@@ -440,7 +474,10 @@ def sample_cached(
     at EOS instead of emitting to full length.
 
     ``fused=True`` runs prefill and decode on ``forward_step_fused`` (the
-    decode kernels on a GPU); combinable with ``graph``."""
+    decode kernels on a GPU); combinable with ``graph``.
+    ``fused_linear=True`` (needs ``fused``) also runs its projections on
+    the decode linear kernel."""
+    _check_fused_linear(fused, fused_linear)
     dev = next(model.parameters()).device if device is None else device
     # the sequence and sampling math live on CPU (matching utils.sample's
     # generator semantics — its fn closure returns .cpu() logits); only
@@ -456,13 +493,14 @@ def sample_cached(
     pos_dev = torch.zeros((), dtype=torch.long, device=dev) if fused else None
     logits = None
     for p in range(start_pos):                           # prefill
-        logits = _eager_step(model, seq[p:p + 1].to(dev), cache, pos_dev)
+        logits = _eager_step(model, seq[p:p + 1].to(dev), cache, pos_dev,
+                             fused_linear)
 
     graphed = None
     if graph and dev.type == "cuda":
         logits = logits.clone()  # the static buffer will be reused
         graphed = GraphedDecodeStep(model, cache, start_pos=start_pos,
-                                    fused=fused)
+                                    fused=fused, fused_linear=fused_linear)
 
     pads_seen = int((seq[:start_pos] == 0).sum())
     for curr_pos in range(start_pos, length):
@@ -484,7 +522,7 @@ def sample_cached(
             else:
                 logits = _eager_step(model,
                                      seq[curr_pos:curr_pos + 1].to(dev),
-                                     cache, pos_dev)
+                                     cache, pos_dev, fused_linear)
 
     remove_after_eos = (seq == 0).long().cumsum(dim=-1) > 1
     return seq * (~remove_after_eos).long()
@@ -500,6 +538,7 @@ def sample_cached_batch(
     device=None,
     graph: bool = False,
     fused: bool = False,
+    fused_linear: bool = False,
 ) -> torch.Tensor:
     """Batched incremental decode: one forward_step advances ALL rows
     (the per-layer caches are batch-first), so serving throughput scales
@@ -515,7 +554,9 @@ def sample_cached_batch(
     each row's output equals its single-row ``sample_cached`` run
     (tests/test_decode.py::test_sample_cached_batch_greedy_parity).
     ``fused=True`` steps with ``forward_step_fused``; combinable with
-    ``graph``."""
+    ``graph``. ``fused_linear=True`` (needs ``fused``) also runs its
+    projections on the decode linear kernel."""
+    _check_fused_linear(fused, fused_linear)
     dev = next(model.parameters()).device if device is None else device
     primes = [torch.as_tensor(p).long().flatten().cpu() for p in primes]
     B = len(primes)
@@ -525,7 +566,8 @@ def sample_cached_batch(
         seq[i, :lens[i]] = p
 
     cache = DecodeCache(model, batch=B, device=dev)
-    graphed = GraphedDecodeStep(model, cache, start_pos=0, fused=fused) \
+    graphed = GraphedDecodeStep(model, cache, start_pos=0, fused=fused,
+                                fused_linear=fused_linear) \
         if (graph and dev.type == "cuda") else None
     # the graphed step owns its device position; the eager fused one needs one
     pos_dev = torch.zeros((), dtype=torch.long, device=dev) \
@@ -539,7 +581,7 @@ def sample_cached_batch(
             logits = graphed.step(seq[:, pos])
         else:
             logits = _eager_step(model, seq[:, pos].to(dev), cache,
-                                 pos_dev)                # (B, V)
+                                 pos_dev, fused_linear)  # (B, V)
         rows = logits.cpu().float()  # no device kernel between replays
         if greedy:
             nxt = rows.argmax(dim=-1)

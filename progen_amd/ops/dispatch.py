@@ -94,6 +94,46 @@ def has_ext_decode() -> bool:
     return _EXT_DECODE is not None
 
 
+# the decode step's linear op with fused epilogues: a third module
+# (progen_amd._C_decode_linear, ops/hip/decode_linear_bindings.cpp)
+_EXT_DECODE_LINEAR: Optional[Any] = None
+_EXT_DECODE_LINEAR_ERR: Optional[str] = None
+_TRIED_DECODE_LINEAR = False
+
+
+def _try_load_decode_linear() -> None:
+    global _EXT_DECODE_LINEAR, _EXT_DECODE_LINEAR_ERR, _TRIED_DECODE_LINEAR
+    if _TRIED_DECODE_LINEAR:
+        return
+    _TRIED_DECODE_LINEAR = True
+    try:
+        _EXT_DECODE_LINEAR = importlib.import_module(
+            "progen_amd._C_decode_linear")
+    except Exception as e:  # noqa: BLE001 - record and re-raise on GPU use
+        _EXT_DECODE_LINEAR = None
+        _EXT_DECODE_LINEAR_ERR = f"{type(e).__name__}: {e}"
+
+
+def ext_decode_linear() -> Any:
+    """Return the loaded decode-linear extension, raising loudly if
+    unavailable — a shape routed to the kernel never falls back."""
+    _try_load_decode_linear()
+    if _EXT_DECODE_LINEAR is None:
+        raise RuntimeError(
+            "progen_amd decode-linear extension "
+            "(progen_amd._C_decode_linear) is not available (import error: "
+            f"{_EXT_DECODE_LINEAR_ERR}). Build it in-tree with "
+            "`python setup.py build_ext --inplace` "
+            "(PYTORCH_ROCM_ARCH=gfx950)."
+        )
+    return _EXT_DECODE_LINEAR
+
+
+def has_ext_decode_linear() -> bool:
+    _try_load_decode_linear()
+    return _EXT_DECODE_LINEAR is not None
+
+
 def use_hip(t, op: str = None) -> bool:
     """True when tensor t lives on a ROCm GPU (→ HIP kernels are mandatory).
 
@@ -103,7 +143,7 @@ def use_hip(t, op: str = None) -> bool:
       the per-kernel bisect lever for the graphed-replay investigation
       (profiles/r02_graphed_nan_investigation.md). Tags: ln, attn, glu,
       sgu, ce, adamw; the fused decode step's ops are dec_ln, dec_attn,
-      dec_sgu.
+      dec_sgu and dec_linear.
     """
     if not t.is_cuda:
         return False

@@ -13,6 +13,7 @@ also the numerics oracle for the kernels.
 from __future__ import annotations
 
 import torch
+import torch.nn.functional as F
 
 from . import dispatch, reference
 
@@ -347,3 +348,55 @@ def decode_sgu(h: torch.Tensor, norm_weight: torch.Tensor,
             float(eps))
     return reference.decode_sgu(h, norm_weight, hist, spatial_weights,
                                 spatial_biases, pos, eps)
+
+
+# ---------------------------------------------------------------------------
+# decode-step linear with fused epilogue (progen_amd._C_decode_linear)
+# ---------------------------------------------------------------------------
+
+DEC_LINEAR_ACTS = ("none", "gelu", "glu")
+# the kernel's own limit on rows (ops/hip/decode_linear_kernels.h)
+DEC_LINEAR_KERNEL_MAX_B = 32
+# largest batch the routing sends to the kernel, set by the end-to-end
+# measurement of profiles/decode_linear.md (the step wins at 1, 8 and 16
+# rows and loses at 32); above it hipBLASLt runs
+DEC_LINEAR_MAX_B = 16
+
+
+def decode_linear_supported(B: int, K: int, N: int, act: str, dtype) -> bool:
+    """True when ``decode_linear`` routes a (B, K) x (N, K) call of ``dtype``
+    with ``act`` to the HIP kernel (given a GPU tensor): the kernel's
+    contract, and the routing limit ``DEC_LINEAR_MAX_B``."""
+    if act not in DEC_LINEAR_ACTS:
+        return False
+    if dtype not in (torch.bfloat16, torch.float32):
+        return False
+    if not 1 <= B <= min(DEC_LINEAR_MAX_B, DEC_LINEAR_KERNEL_MAX_B):
+        return False
+    if K < 64 or K % 64 != 0:
+        return False
+    return N >= 16 and N % (32 if act == "glu" else 16) == 0
+
+
+def decode_linear(x: torch.Tensor, w: torch.Tensor, bias=None,
+                  act: str = "none") -> torch.Tensor:
+    """act(x @ w^T + bias) for the (B, K) rows of a decode step
+    (reference.decode_linear). On a GPU a supported shape runs the HIP
+    kernel, which adds the bias and applies the activation on its fp32
+    accumulators; any other shape is a plain GEMM and goes to hipBLASLt
+    like every other one, followed by the GLU/GELU kernel."""
+    if act not in DEC_LINEAR_ACTS:
+        raise ValueError(f"decode_linear: unknown act {act!r}")
+    if dispatch.use_hip(x, "dec_linear") and x.dim() == 2 and w.dim() == 2 \
+            and x.dtype == w.dtype \
+            and decode_linear_supported(x.shape[0], x.shape[1], w.shape[0],
+                                        act, x.dtype):
+        return dispatch.ext_decode_linear().dec_linear(
+            x.contiguous(), w.contiguous(),
+            None if bias is None else bias.contiguous(), act)
+    h = F.linear(x, w, bias)
+    if act == "glu":
+        return glu_gelu(h)
+    if act == "gelu":
+        return gelu(h)
+    return h

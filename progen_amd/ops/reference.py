@@ -395,3 +395,18 @@ def decode_sgu(
     gate_out = torch.einsum("n,bnd->bd", w_row, rows) + \
         bias.index_select(0, p)[0].to(hist.dtype)
     return xa * gate_out
+
+
+def decode_linear(x: torch.Tensor, w: torch.Tensor, bias, act: str = "none"
+                  ) -> torch.Tensor:
+    """``F.linear`` followed by the activation, in the input dtype: what the
+    decode step computes with separate ops. ``act``: "none", "gelu" or
+    "glu" (the output is then half as wide, ``glu_gelu``'s pairing)."""
+    h = F.linear(x, w, bias)
+    if act == "glu":
+        return glu_gelu(h)
+    if act == "gelu":
+        return gelu(h)
+    if act != "none":
+        raise ValueError(f"decode_linear: unknown act {act!r}")
+    return h

@@ -31,7 +31,13 @@ load_dotenv()  # reference: sample.py:1-2
 @click.option('--fused', default=False, is_flag=True,
               help='with --cached: run the step on the fused decode kernels '
                    '(combinable with --graph)')
-def main(seed, checkpoint_path, prime, fast, cached, graph, fused):
+@click.option('--fused-linear', 'fused_linear', default=False, is_flag=True,
+              help='with --fused: run the step\'s projections on the decode '
+                   'linear kernel (bias and GLU/GELU folded in)')
+def main(seed, checkpoint_path, prime, fast, cached, graph, fused,
+         fused_linear):
+    if fused_linear and not fused:
+        raise click.UsageError('--fused-linear needs --fused')
     from progen_amd.tuning import enable_tuned_gemms
     enable_tuned_gemms()
     _, get_last_checkpoint, _ = get_checkpoint_fns(checkpoint_path)
@@ -75,7 +81,7 @@ def main(seed, checkpoint_path, prime, fast, cached, graph, fused):
         from progen_amd.decode import sample_cached
         sampled = sample_cached(module, prime_tensor, seq_len, top_k=25,
                                 add_bos=True, generator=g, graph=graph,
-                                fused=fused)
+                                fused=fused, fused_linear=fused_linear)
     elif fast:
         sampled = sample_fast(fwd, prime_tensor, seq_len, top_k=25,
                               add_bos=True, generator=g,

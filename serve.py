@@ -44,8 +44,11 @@ from progen_amd.utils import load_dotenv
 
 def create_app(module: ProGenBase, cfg: ProGenConfig, *,
                graph: bool = False, fused: bool = False,
+               fused_linear: bool = False,
                meta: Optional[dict] = None):
     """Build the FastAPI app around a ready (device-placed, eval) module."""
+    if fused_linear and not fused:
+        raise ValueError("fused_linear=True needs fused=True")
     from fastapi import FastAPI, HTTPException
     from pydantic import BaseModel
 
@@ -59,6 +62,7 @@ def create_app(module: ProGenBase, cfg: ProGenConfig, *,
         "device": str(device),
         "graph": bool(graph and device.type == "cuda"),
         "fused": bool(fused),
+        "fused_linear": bool(fused_linear),
         **(meta or {}),
     }
 
@@ -103,7 +107,8 @@ def create_app(module: ProGenBase, cfg: ProGenConfig, *,
         with lock, torch.no_grad():
             out = sample_cached_batch(module, rows, length, top_k=top_k,
                                       generator=gen, graph=info["graph"],
-                                      fused=info["fused"])
+                                      fused=info["fused"],
+                                      fused_linear=info["fused_linear"])
         ms = (time.perf_counter() - t0) * 1e3
         seqs, toks_out = [], []
         for row, prime_row in zip(out, rows):
@@ -149,13 +154,19 @@ def load_module(checkpoint_path: str):
 @click.option("--fused", default=False, is_flag=True,
               help="run the per-token step on the fused decode kernels "
                    "(combinable with --graph)")
-def main(checkpoint_path, host, port, graph, fused):
+@click.option("--fused-linear", "fused_linear", default=False, is_flag=True,
+              help="with --fused: run the step's projections on the decode "
+                   "linear kernel (bias and GLU/GELU folded in)")
+def main(checkpoint_path, host, port, graph, fused, fused_linear):
+    if fused_linear and not fused:
+        raise click.UsageError("--fused-linear needs --fused")
     load_dotenv()
     from progen_amd.tuning import enable_tuned_gemms
     enable_tuned_gemms()
     import uvicorn
     module, cfg, meta = load_module(checkpoint_path)
-    app = create_app(module, cfg, graph=graph, fused=fused, meta=meta)
+    app = create_app(module, cfg, graph=graph, fused=fused,
+                     fused_linear=fused_linear, meta=meta)
     uvicorn.run(app, host=host, port=port, log_level="info")
 
 

@@ -1,5 +1,5 @@
-"""In-tree build of the progen_amd._C and progen_amd._C_decode HIP
-extensions (gfx950 only).
+"""In-tree build of the progen_amd._C, progen_amd._C_decode and
+progen_amd._C_decode_linear HIP extensions (gfx950 only).
 
     PYTORCH_ROCM_ARCH=gfx950 python setup.py build_ext --inplace
 
@@ -38,6 +38,13 @@ DECODE_SOURCES = [
     "progen_amd/ops/hip/decode_sgu.hip",
 ]
 
+# the decode step's linear op with fused epilogues; a third module, because
+# the export lists of the two above are pinned
+DECODE_LINEAR_SOURCES = [
+    "progen_amd/ops/hip/decode_linear_bindings.cpp",
+    "progen_amd/ops/hip/decode_linear.hip",
+]
+
 COMPILE_ARGS = {
     "cxx": ["-O3", "-std=c++17"],
     "nvcc": ["-O3", "-std=c++17"],
@@ -54,6 +61,11 @@ setup(
         CUDAExtension(
             name="progen_amd._C_decode",
             sources=DECODE_SOURCES,
+            extra_compile_args=COMPILE_ARGS,
+        ),
+        CUDAExtension(
+            name="progen_amd._C_decode_linear",
+            sources=DECODE_LINEAR_SOURCES,
             extra_compile_args=COMPILE_ARGS,
         ),
     ],
