@@ -30,7 +30,7 @@ __global__ void step_inc_kernel(int* step, const float* clip_coef) {
   if (threadIdx.x == 0 && blockIdx.x == 0 && step_ok(*clip_coef)) *step += 1;
 }
 
-template <bool IS_BF16>
+template <bool BF>
 __global__ __launch_bounds__(ADAMW_BLOCK) void fused_adamw_kernel(
     float* __restrict__ master, void* __restrict__ params,
     const void* __restrict__ grads, float* __restrict__ exp_avg,
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(ADAMW_BLOCK) void fused_adamw_kernel(
     const long long e = ends[c];
     const float wdc = decay_flags[c] ? wd : 0.f;
     for (long long i = s + threadIdx.x; i < e; i += ADAMW_BLOCK) {
-      float g = IS_BF16 ? bf2f(((const short*)grads)[i]) : ((const float*)grads)[i];
+      float g = ld1<BF>(grads, i);
       g *= grad_scale * clip;
       const long long si = i - shard_off;
       float m = exp_avg[si] = b1 * exp_avg[si] + (1.f - b1) * g;
@@ -62,8 +62,7 @@ __global__ __launch_bounds__(ADAMW_BLOCK) void fused_adamw_kernel(
       float p = master[si];
       p -= lr * (mhat / (sqrtf(vhat) + eps) + wdc * p);
       master[si] = p;
-      if (IS_BF16) ((short*)params)[i] = f2bf(p);
-      else ((float*)params)[i] = p;
+      st1<BF>(params, i, p);
     }
   }
 }
@@ -72,24 +71,17 @@ __global__ __launch_bounds__(ADAMW_BLOCK) void fused_adamw_kernel(
 // accumulation), partials combined with a device-scope atomicAdd — the
 // clip coefficient then stays on device (no host sync, no fp32 copy of
 // the 2.7 GB bf16 grad buffer).
-template <bool IS_BF16>
+template <bool BF>
 __global__ __launch_bounds__(ADAMW_BLOCK) void grad_sumsq_kernel(
     const void* __restrict__ grads, float* __restrict__ out, long long nv) {
-  constexpr int VLEN = IS_BF16 ? 8 : 4;
   float acc = 0.f;
   for (long long i = blockIdx.x * (long long)ADAMW_BLOCK + threadIdx.x;
        i < nv; i += (long long)gridDim.x * ADAMW_BLOCK) {
-    if (IS_BF16) {
-      bf16x8 v = ((const bf16x8*)grads)[i];
+    const vec16_t<BF> v = ((const vec16_t<BF>*)grads)[i];
 #pragma unroll
-      for (int j = 0; j < VLEN; ++j) {
-        float f = bf2f(((short*)&v)[j]);
-        acc += f * f;
-      }
-    } else {
-      f32x4 v = ((const f32x4*)grads)[i];
-#pragma unroll
-      for (int j = 0; j < VLEN; ++j) acc += ((float*)&v)[j] * ((float*)&v)[j];
+    for (int j = 0; j < vec16<BF>::N; ++j) {
+      const float f = vget<BF>(v, j);
+      acc += f * f;
     }
   }
   acc = wave_sum(acc);

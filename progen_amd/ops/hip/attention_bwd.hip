@@ -84,17 +84,13 @@
 //                                    A-frags read it b128, dQ A-frags
 //                                    via tr; per chunk)
 
-#include "common.h"
+#include "lds_images.h"  // swz, and uk4 for the dS^T image
 
 #define DH 64
 #define KT 64
 #define ATTN_WAVES 4
 #define ATTN_BLOCK (ATTN_WAVES * WAVE)
 #define NEG_INF (-1e30f)
-
-__device__ __forceinline__ int swz(int row, int byte_in_row) {
-  return (byte_in_row ^ ((row & 7) << 4));
-}
 
 __device__ __forceinline__ void load_rope(const float* rsin,
                                           const float* rcos, long long pos,
@@ -104,17 +100,6 @@ __device__ __forceinline__ void load_rope(const float* rsin,
   *(f32x4*)(cv) = *(const f32x4*)(rcos + pos * DH + d0);
   *(f32x4*)(cv + 4) = *(const f32x4*)(rcos + pos * DH + d0 + 4);
 }
-
-// per-key 32-B XOR window for the dS^T image (128-B rows): the half-
-// wave's 8 key-rows {kb..kb+3, kb+8..kb+11} split 4/4 by parity (row
-// base 32*(key&1) dwords) and within a parity v(key) is a bijection
-// onto 0..3, so the 8 rows cover all 64 banks -> zero-conflict tr
-// reads. v*32 <= 96 B stays inside the 128-B row (uk-style *32 from
-// the wgrad image would escape it).
-__device__ __forceinline__ int uk4(int k) { return ((k & 2) >> 1) | ((k & 8) >> 2); }
-
-typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 bf16x4t;
-#define AS3 __attribute__((address_space(3)))
 
 #define V5_WAVES 8
 #define V5_BLOCK (V5_WAVES * WAVE)

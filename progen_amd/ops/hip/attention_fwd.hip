@@ -36,7 +36,7 @@
 //
 // dim_head is fixed at 64 (the ProGen family's head size).
 
-#include "common.h"
+#include "lds_images.h"
 
 #define DH 64
 #define KT 64                 // keys per tile
@@ -46,19 +46,10 @@
 #define QB (MF * 16)          // q rows per wave
 #define NEG_INF (-1e30f)
 
-__device__ __forceinline__ int swz(int row, int byte_in_row) {
-  return (byte_in_row ^ ((row & 7) << 4));
-}
-
-// per-key 32-B XOR window for the LINEAR [key][dh] V image (128-B
-// rows): the PV B-fragments are ds_read_b64_tr_b16 transposed reads
-// whose half-wave covers key rows {kb..kb+3, kb+8..kb+11}; v(k) is a
-// bijection onto 0..3 within each row parity, so the 8 rows cover all
-// 64 banks (same derivation as attention_bwd.hip's dS^T image)
-__device__ __forceinline__ int uk4(int k) { return ((k & 2) >> 1) | ((k & 8) >> 2); }
-
-typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 bf16x4t;
-#define AS3 __attribute__((address_space(3)))
+// swz (lds_images.h) swizzles the K and P images. The LINEAR [key][dh] V
+// image (128-B rows) takes the per-key 32-B XOR window uk4 instead: the PV
+// B-fragments are ds_read_b64_tr_b16 transposed reads whose half-wave
+// covers key rows {kb..kb+3, kb+8..kb+11} (derivation in lds_images.h).
 
 __global__ __launch_bounds__(ATTN_BLOCK) void attn_fwd_kernel(
     const short* __restrict__ qkv,   // (B, N, 3*H*DH) bf16, PRE-ROTATED

@@ -147,9 +147,45 @@ __device__ __forceinline__ float ld1(const void* p, long long idx) {
 }
 
 template <bool BF>
+__device__ __forceinline__ void st1(void* p, long long idx, float v) {
+  if constexpr (BF) ((short*)p)[idx] = f2bf(v);
+  else ((float*)p)[idx] = v;
+}
+
+template <bool BF>
 __device__ __forceinline__ float round_trip(float x) {
   if constexpr (BF) return bf2f(f2bf(x));
   else return x;
+}
+
+// The 16 B vector of a storage type, for kernels in which one thread owns one
+// 16 B load: 8 bf16 or FOUR fp32. (ld8 hands a thread 8 elements of either
+// type; which elements a thread owns fixes the order of every sum it feeds,
+// so a kernel stays with the one it was written on.) vget/vset read and
+// write element j as fp32; vset rounds to the storage type.
+template <bool BF>
+struct vec16 {
+  using type = f32x4;
+  static constexpr int N = 4;
+};
+template <>
+struct vec16<true> {
+  using type = bf16x8;
+  static constexpr int N = 8;
+};
+template <bool BF>
+using vec16_t = typename vec16<BF>::type;
+
+template <bool BF>
+__device__ __forceinline__ float vget(const vec16_t<BF>& v, int j) {
+  if constexpr (BF) return bf2f(v[j]);
+  else return v[j];
+}
+
+template <bool BF>
+__device__ __forceinline__ void vset(vec16_t<BF>& v, int j, float x) {
+  if constexpr (BF) v[j] = f2bf(x);
+  else v[j] = x;
 }
 
 // sum over a 256-thread block, result in every thread. ``red`` holds 4

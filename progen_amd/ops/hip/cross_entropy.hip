@@ -11,27 +11,26 @@
 #define CE_WAVES 4
 #define CE_BLOCK (CE_WAVES * WAVE)
 
-template <bool IS_BF16>
+template <bool BF>
 __global__ __launch_bounds__(CE_BLOCK) void ce_fwd_kernel(
-    const void* __restrict__ logits_, const long long* __restrict__ targets,
+    const void* __restrict__ logits, const long long* __restrict__ targets,
     float* __restrict__ nll, float* __restrict__ lse_out, long long R, int V) {
   const long long row = blockIdx.x * (long long)CE_WAVES + threadIdx.x / WAVE;
   if (row >= R) return;
   const int lane = threadIdx.x % WAVE;
 
-  const short* lb = IS_BF16 ? ((const short*)logits_) + row * V : nullptr;
-  const float* lf = IS_BF16 ? nullptr : ((const float*)logits_) + row * V;
+  const long long base = row * V;
 
   float m = -INFINITY;
   for (int v = lane; v < V; v += WAVE) {
-    float x = IS_BF16 ? bf2f(lb[v]) : lf[v];
+    float x = ld1<BF>(logits, base + v);
     m = fmaxf(m, x);
   }
   m = wave_max(m);
 
   float s = 0.f;
   for (int v = lane; v < V; v += WAVE) {
-    float x = IS_BF16 ? bf2f(lb[v]) : lf[v];
+    float x = ld1<BF>(logits, base + v);
     s += __expf(x - m);
   }
   s = wave_sum(s);
@@ -39,34 +38,31 @@ __global__ __launch_bounds__(CE_BLOCK) void ce_fwd_kernel(
 
   if (lane == 0) {
     const long long t = targets[row];
-    const float xt = IS_BF16 ? bf2f(lb[t]) : lf[t];
+    const float xt = ld1<BF>(logits, base + t);
     nll[row] = lse - xt;
     lse_out[row] = lse;
   }
 }
 
-template <bool IS_BF16>
+template <bool BF>
 __global__ __launch_bounds__(CE_BLOCK) void ce_bwd_kernel(
-    const float* __restrict__ dnll, const void* __restrict__ logits_,
+    const float* __restrict__ dnll, const void* __restrict__ logits,
     const long long* __restrict__ targets, const float* __restrict__ lse,
-    void* __restrict__ dlogits_, long long R, int V) {
+    void* __restrict__ dlogits, long long R, int V) {
   const long long row = blockIdx.x * (long long)CE_WAVES + threadIdx.x / WAVE;
   if (row >= R) return;
   const int lane = threadIdx.x % WAVE;
 
-  const short* lb = IS_BF16 ? ((const short*)logits_) + row * V : nullptr;
-  const float* lf = IS_BF16 ? nullptr : ((const float*)logits_) + row * V;
-  short* db = IS_BF16 ? ((short*)dlogits_) + row * V : nullptr;
-  float* df = IS_BF16 ? nullptr : ((float*)dlogits_) + row * V;
+  const long long base = row * V;
 
   const float d = dnll[row];
   const float l = lse[row];
   const long long t = targets[row];
 
   for (int v = lane; v < V; v += WAVE) {
-    float x = IS_BF16 ? bf2f(lb[v]) : lf[v];
+    float x = ld1<BF>(logits, base + v);
     float g = d * (__expf(x - l) - (v == (int)t ? 1.f : 0.f));
-    if (IS_BF16) db[v] = f2bf(g); else df[v] = g;
+    st1<BF>(dlogits, base + v, g);
   }
 }
 

@@ -81,12 +81,6 @@ __device__ __forceinline__ void widen16(const raw16<BF>& r, float* x) {
   }
 }
 
-template <bool BF>
-__device__ __forceinline__ void st1(void* p, long long idx, float v) {
-  if constexpr (BF) ((short*)p)[idx] = f2bf(v);
-  else ((float*)p)[idx] = v;
-}
-
 // sum over the waves in wave order, bias, activation, one rounding.
 // ``part`` is [wave][half][tile-local index]; ``idx`` the tile-local index
 // of output (b, n0 + nl), ``stride`` the floats of one wave.

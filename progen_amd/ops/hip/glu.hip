@@ -1,7 +1,8 @@
 // GLU-GELU epilogue of the feedforward (reference: progen.py:139-143):
 //   glu:  y = a * gelu(g)  with (a, g) = split(h, 2, dim=-1)
 //   gelu: y = gelu(h)
-// Memory-bound elementwise kernels, 16 B/lane vectorized, grid-stride.
+// Memory-bound elementwise kernels, one 16 B vector (vec16_t<BF>) per lane
+// and trip, grid-stride.
 
 #include "common.h"
 
@@ -10,91 +11,85 @@
 // 2-D grid (columns x row-stripes): the flat-index form cost two
 // 64-bit integer divisions per iteration — a long VALU sequence on a
 // kernel this loop-dense
-template <typename VEC, bool IS_BF16>
+template <bool BF>
 __global__ __launch_bounds__(GLU_BLOCK) void glu_fwd_kernel(
-    const VEC* __restrict__ h, VEC* __restrict__ y, long long rows, int Hv) {
-  constexpr int VLEN = IS_BF16 ? 8 : 4;
+    const void* __restrict__ h_, void* __restrict__ y_, long long rows,
+    int Hv) {
+  using VEC = vec16_t<BF>;
+  const VEC* h = (const VEC*)h_;
+  VEC* y = (VEC*)y_;
   const int i = blockIdx.x * GLU_BLOCK + (int)threadIdx.x;
   if (i >= Hv) return;
   for (long long row = blockIdx.y; row < rows; row += gridDim.y) {
-    VEC va = h[row * 2 * Hv + i];
-    VEC vg = h[row * 2 * Hv + Hv + i];
+    const VEC va = h[row * 2 * Hv + i];
+    const VEC vg = h[row * 2 * Hv + Hv + i];
     VEC o;
 #pragma unroll
-    for (int j = 0; j < VLEN; ++j) {
-      float a = IS_BF16 ? bf2f(((short*)&va)[j]) : ((float*)&va)[j];
-      float g = IS_BF16 ? bf2f(((short*)&vg)[j]) : ((float*)&vg)[j];
-      float r = a * gelu_tanh(g);
-      if (IS_BF16) ((short*)&o)[j] = f2bf(r); else ((float*)&o)[j] = r;
-    }
+    for (int j = 0; j < vec16<BF>::N; ++j)
+      vset<BF>(o, j, vget<BF>(va, j) * gelu_tanh(vget<BF>(vg, j)));
     y[row * Hv + i] = o;
   }
 }
 
-template <typename VEC, bool IS_BF16>
+template <bool BF>
 __global__ __launch_bounds__(GLU_BLOCK) void glu_bwd_kernel(
-    const VEC* __restrict__ dy, const VEC* __restrict__ h,
-    VEC* __restrict__ dh, long long rows, int Hv) {
-  constexpr int VLEN = IS_BF16 ? 8 : 4;
+    const void* __restrict__ dy_, const void* __restrict__ h_,
+    void* __restrict__ dh_, long long rows, int Hv) {
+  using VEC = vec16_t<BF>;
+  const VEC *dy = (const VEC*)dy_, *h = (const VEC*)h_;
+  VEC* dh = (VEC*)dh_;
   const int i = blockIdx.x * GLU_BLOCK + (int)threadIdx.x;
   if (i >= Hv) return;
   for (long long row = blockIdx.y; row < rows; row += gridDim.y) {
-    VEC va = h[row * 2 * Hv + i];
-    VEC vg = h[row * 2 * Hv + Hv + i];
-    VEC vdy = dy[row * Hv + i];
+    const VEC va = h[row * 2 * Hv + i];
+    const VEC vg = h[row * 2 * Hv + Hv + i];
+    const VEC vdy = dy[row * Hv + i];
     VEC da, dg;
 #pragma unroll
-    for (int j = 0; j < VLEN; ++j) {
-      float a = IS_BF16 ? bf2f(((short*)&va)[j]) : ((float*)&va)[j];
-      float g = IS_BF16 ? bf2f(((short*)&vg)[j]) : ((float*)&vg)[j];
-      float d = IS_BF16 ? bf2f(((short*)&vdy)[j]) : ((float*)&vdy)[j];
+    for (int j = 0; j < vec16<BF>::N; ++j) {
+      const float d = vget<BF>(vdy, j);
       float gv, gg;
-      gelu_tanh_both(g, &gv, &gg);
-      float rda = d * gv;
-      float rdg = d * a * gg;
-      if (IS_BF16) { ((short*)&da)[j] = f2bf(rda); ((short*)&dg)[j] = f2bf(rdg); }
-      else { ((float*)&da)[j] = rda; ((float*)&dg)[j] = rdg; }
+      gelu_tanh_both(vget<BF>(vg, j), &gv, &gg);
+      vset<BF>(da, j, d * gv);
+      vset<BF>(dg, j, d * vget<BF>(va, j) * gg);
     }
     dh[row * 2 * Hv + i] = da;
     dh[row * 2 * Hv + Hv + i] = dg;
   }
 }
 
-template <typename VEC, bool IS_BF16>
+template <bool BF>
 __global__ __launch_bounds__(GLU_BLOCK) void gelu_fwd_kernel(
-    const VEC* __restrict__ h, VEC* __restrict__ y, long long total) {
-  constexpr int VLEN = IS_BF16 ? 8 : 4;
+    const void* __restrict__ h_, void* __restrict__ y_, long long total) {
+  using VEC = vec16_t<BF>;
+  const VEC* h = (const VEC*)h_;
+  VEC* y = (VEC*)y_;
   for (long long idx = blockIdx.x * (long long)GLU_BLOCK + threadIdx.x;
        idx < total; idx += (long long)gridDim.x * GLU_BLOCK) {
-    VEC v = h[idx];
+    const VEC v = h[idx];
     VEC o;
 #pragma unroll
-    for (int j = 0; j < VLEN; ++j) {
-      float g = IS_BF16 ? bf2f(((short*)&v)[j]) : ((float*)&v)[j];
-      float r = gelu_tanh(g);
-      if (IS_BF16) ((short*)&o)[j] = f2bf(r); else ((float*)&o)[j] = r;
-    }
+    for (int j = 0; j < vec16<BF>::N; ++j)
+      vset<BF>(o, j, gelu_tanh(vget<BF>(v, j)));
     y[idx] = o;
   }
 }
 
-template <typename VEC, bool IS_BF16>
+template <bool BF>
 __global__ __launch_bounds__(GLU_BLOCK) void gelu_bwd_kernel(
-    const VEC* __restrict__ dy, const VEC* __restrict__ h,
-    VEC* __restrict__ dh, long long total) {
-  constexpr int VLEN = IS_BF16 ? 8 : 4;
+    const void* __restrict__ dy_, const void* __restrict__ h_,
+    void* __restrict__ dh_, long long total) {
+  using VEC = vec16_t<BF>;
+  const VEC *dy = (const VEC*)dy_, *h = (const VEC*)h_;
+  VEC* dh = (VEC*)dh_;
   for (long long idx = blockIdx.x * (long long)GLU_BLOCK + threadIdx.x;
        idx < total; idx += (long long)gridDim.x * GLU_BLOCK) {
-    VEC v = h[idx];
-    VEC vdy = dy[idx];
+    const VEC v = h[idx];
+    const VEC vdy = dy[idx];
     VEC o;
 #pragma unroll
-    for (int j = 0; j < VLEN; ++j) {
-      float g = IS_BF16 ? bf2f(((short*)&v)[j]) : ((float*)&v)[j];
-      float d = IS_BF16 ? bf2f(((short*)&vdy)[j]) : ((float*)&vdy)[j];
-      float r = d * gelu_tanh_grad(g);
-      if (IS_BF16) ((short*)&o)[j] = f2bf(r); else ((float*)&o)[j] = r;
-    }
+    for (int j = 0; j < vec16<BF>::N; ++j)
+      vset<BF>(o, j, vget<BF>(vdy, j) * gelu_tanh_grad(vget<BF>(v, j)));
     dh[idx] = o;
   }
 }
@@ -119,55 +114,45 @@ extern "C" {
 
 hipError_t glu_fwd_launch(const void* h, void* y, long long rows, int H,
                           bool is_bf16, hipStream_t stream) {
-  if (is_bf16) {
-    int Hv = H / 8;
-    glu_fwd_kernel<bf16x8, true><<<glu_grid2(rows, Hv), GLU_BLOCK, 0, stream>>>(
-        (const bf16x8*)h, (bf16x8*)y, rows, Hv);
-  } else {
-    int Hv = H / 4;
-    glu_fwd_kernel<f32x4, false><<<glu_grid2(rows, Hv), GLU_BLOCK, 0, stream>>>(
-        (const f32x4*)h, (f32x4*)y, rows, Hv);
-  }
+  const int Hv = H / (is_bf16 ? 8 : 4);
+  const dim3 grid = glu_grid2(rows, Hv);
+  if (is_bf16)
+    glu_fwd_kernel<true><<<grid, GLU_BLOCK, 0, stream>>>(h, y, rows, Hv);
+  else
+    glu_fwd_kernel<false><<<grid, GLU_BLOCK, 0, stream>>>(h, y, rows, Hv);
   return hipGetLastError();
 }
 
 hipError_t glu_bwd_launch(const void* dy, const void* h, void* dh,
                           long long rows, int H, bool is_bf16,
                           hipStream_t stream) {
-  if (is_bf16) {
-    int Hv = H / 8;
-    glu_bwd_kernel<bf16x8, true><<<glu_grid2(rows, Hv), GLU_BLOCK, 0, stream>>>(
-        (const bf16x8*)dy, (const bf16x8*)h, (bf16x8*)dh, rows, Hv);
-  } else {
-    int Hv = H / 4;
-    glu_bwd_kernel<f32x4, false><<<glu_grid2(rows, Hv), GLU_BLOCK, 0, stream>>>(
-        (const f32x4*)dy, (const f32x4*)h, (f32x4*)dh, rows, Hv);
-  }
+  const int Hv = H / (is_bf16 ? 8 : 4);
+  const dim3 grid = glu_grid2(rows, Hv);
+  if (is_bf16)
+    glu_bwd_kernel<true><<<grid, GLU_BLOCK, 0, stream>>>(dy, h, dh, rows, Hv);
+  else
+    glu_bwd_kernel<false><<<grid, GLU_BLOCK, 0, stream>>>(dy, h, dh, rows, Hv);
   return hipGetLastError();
 }
 
 hipError_t gelu_fwd_launch(const void* h, void* y, long long total_elems,
                            bool is_bf16, hipStream_t stream) {
-  long long tv = total_elems / (is_bf16 ? 8 : 4);
+  const long long tv = total_elems / (is_bf16 ? 8 : 4);
   if (is_bf16)
-    gelu_fwd_kernel<bf16x8, true><<<glu_grid(tv), GLU_BLOCK, 0, stream>>>(
-        (const bf16x8*)h, (bf16x8*)y, tv);
+    gelu_fwd_kernel<true><<<glu_grid(tv), GLU_BLOCK, 0, stream>>>(h, y, tv);
   else
-    gelu_fwd_kernel<f32x4, false><<<glu_grid(tv), GLU_BLOCK, 0, stream>>>(
-        (const f32x4*)h, (f32x4*)y, tv);
+    gelu_fwd_kernel<false><<<glu_grid(tv), GLU_BLOCK, 0, stream>>>(h, y, tv);
   return hipGetLastError();
 }
 
 hipError_t gelu_bwd_launch(const void* dy, const void* h, void* dh,
                            long long total_elems, bool is_bf16,
                            hipStream_t stream) {
-  long long tv = total_elems / (is_bf16 ? 8 : 4);
+  const long long tv = total_elems / (is_bf16 ? 8 : 4);
   if (is_bf16)
-    gelu_bwd_kernel<bf16x8, true><<<glu_grid(tv), GLU_BLOCK, 0, stream>>>(
-        (const bf16x8*)dy, (const bf16x8*)h, (bf16x8*)dh, tv);
+    gelu_bwd_kernel<true><<<glu_grid(tv), GLU_BLOCK, 0, stream>>>(dy, h, dh, tv);
   else
-    gelu_bwd_kernel<f32x4, false><<<glu_grid(tv), GLU_BLOCK, 0, stream>>>(
-        (const f32x4*)dy, (const f32x4*)h, (f32x4*)dh, tv);
+    gelu_bwd_kernel<false><<<glu_grid(tv), GLU_BLOCK, 0, stream>>>(dy, h, dh, tv);
   return hipGetLastError();
 }
 

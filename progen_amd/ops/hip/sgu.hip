@@ -24,27 +24,23 @@
 // naturally k-contiguous; the W tile reuse across (b, d) keeps them
 // L2-resident).
 
-#include "common.h"
+#include "lds_images.h"
 
 #define SGU_WAVES 4
 #define SGU_BLOCK (SGU_WAVES * WAVE)
 
-// XOR windows for tr-read images (derivations: wgrad probe header for
-// 512-B rows, attention_bwd.hip for 128-B rows)
+// XOR window for tr-read images with 512-B rows (derivation: wgrad probe
+// header); the 128-B-row images take uk4 of lds_images.h
 __device__ __forceinline__ int uk512(int k) { return (k & 3) | ((k & 8) >> 1); }
-__device__ __forceinline__ int uk128(int k) { return ((k & 2) >> 1) | ((k & 8) >> 2); }
-
-typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 sgu_bf16x4t;
-#define SGU_AS3 __attribute__((address_space(3)))
 
 // one MFMA fragment from two ds_read_b64_tr_b16 of a row-major image
 __device__ __forceinline__ bf16x8 sgu_frag_tr(const char* img, int rowbytes,
                                               int r1, int r2, int colb1,
                                               int colb2) {
-  auto p1 = (SGU_AS3 sgu_bf16x4t*)(img + r1 * rowbytes + colb1);
-  auto p2 = (SGU_AS3 sgu_bf16x4t*)(img + r2 * rowbytes + colb2);
-  sgu_bf16x4t a = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(p1);
-  sgu_bf16x4t b = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(p2);
+  auto p1 = (AS3 bf16x4t*)(img + r1 * rowbytes + colb1);
+  auto p2 = (AS3 bf16x4t*)(img + r2 * rowbytes + colb2);
+  bf16x4t a = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(p1);
+  bf16x4t b = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(p2);
   bf16x8 o;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -52,10 +48,6 @@ __device__ __forceinline__ bf16x8 sgu_frag_tr(const char* img, int rowbytes,
     ((__bf16*)&o)[j + 4] = b[j];
   }
   return o;
-}
-
-__device__ __forceinline__ int swz(int row, int byte_in_row) {
-  return (byte_in_row ^ ((row & 7) << 4));
 }
 
 // ---------------------------------------------------------------------------
@@ -109,7 +101,7 @@ __global__ __launch_bounds__(SGU_BLOCK) void sgu_fwd_kernel(
         const int dd = (u & 7) * 8;
         bf16x8 v = *(const bf16x8*)(g_ln + bND + (long long)(t * 64 + k) * D +
                                     d0 + dd);
-        *(bf16x8*)(gt_lds + k * 128 + ((dd * 2) ^ (uk128(k) * 32))) = v;
+        *(bf16x8*)(gt_lds + k * 128 + ((dd * 2) ^ (uk4(k) * 32))) = v;
       }
     }
     __syncthreads();
@@ -127,7 +119,7 @@ __global__ __launch_bounds__(SGU_BLOCK) void sgu_fwd_kernel(
         for (int n = 0; n < 4; ++n) {
           const int cb = (n * 16 + (l15 & 3) * 4) * 2;
           bfr[n] = sgu_frag_tr(gt_lds, 128, r1, r2,
-                               cb ^ (uk128(r1) * 32), cb ^ (uk128(r2) * 32));
+                               cb ^ (uk4(r1) * 32), cb ^ (uk4(r2) * 32));
         }
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
@@ -216,7 +208,7 @@ __global__ __launch_bounds__(SGU_BLOCK) void sgu_dgate_kernel(
         const int dd = (u & 7) * 8;
         bf16x8 v = *(const bf16x8*)(t_in + bND + (long long)(t * 64 + m) * D +
                                     d0 + dd);
-        *(bf16x8*)(tt_lds + m * 128 + ((dd * 2) ^ (uk128(m) * 32))) = v;
+        *(bf16x8*)(tt_lds + m * 128 + ((dd * 2) ^ (uk4(m) * 32))) = v;
       }
     }
     {
@@ -250,7 +242,7 @@ __global__ __launch_bounds__(SGU_BLOCK) void sgu_dgate_kernel(
         for (int n = 0; n < 4; ++n) {
           const int cb = (n * 16 + (l15 & 3) * 4) * 2;
           bfr[n] = sgu_frag_tr(tt_lds, 128, r1, r2,
-                               cb ^ (uk128(r1) * 32), cb ^ (uk128(r2) * 32));
+                               cb ^ (uk4(r1) * 32), cb ^ (uk4(r2) * 32));
         }
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
