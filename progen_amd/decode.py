@@ -325,6 +325,46 @@ def forward_step_fused(model: ProGenBase, token: torch.Tensor,
     return linear(y, model.to_logits)
 
 
+class DeviceSampler:
+    """Sampling state that lives on the model's device, for
+    ``OF.decode_sample``: the sequences ``seq`` (B, L), the prime lengths
+    ``lens``, the pad counts ``pads`` over written tokens and the Philox
+    ``seed`` (1,), all int64.
+
+    Every tensor is initialised by a host-to-device COPY of a host tensor,
+    never by a device kernel, so building one between graph replays keeps
+    the pure-replay rule. ``top_k`` None is no top-k mask; ``seed`` None is
+    greedy argmax, else an int in [0, 2^63). The uniform stream is the
+    kernel's own Philox4x32-10 (ops/reference.py, decode_sample_uniform),
+    not torch's generator stream."""
+
+    def __init__(self, seq: torch.Tensor, lens, top_k: Optional[int],
+                 seed: Optional[int], device):
+        seq = torch.as_tensor(seq).long().cpu()
+        if seq.dim() != 2:
+            raise ValueError("DeviceSampler: seq must be (B, L)")
+        self.top_k = 0 if top_k is None else int(top_k)
+        if self.top_k < 0:
+            raise ValueError(f"top_k must be >= 0, got {top_k}")
+        self.greedy = seed is None
+        if seed is not None and not 0 <= int(seed) < 2 ** 63:
+            raise ValueError(f"seed must be in [0, 2^63), got {seed}")
+        self.seq = seq.contiguous().to(device, copy=True)  # never the caller's
+        self.lens = torch.tensor([int(n) for n in lens],
+                                 dtype=torch.long).to(device)
+        # position 0 is written at entry; the unfilled tail must not count
+        self.pads = (seq[:, 0] == 0).long().to(device)
+        self.seed = torch.tensor([0 if seed is None else int(seed)],
+                                 dtype=torch.long).to(device)
+
+    def sample(self, logits: torch.Tensor, pos_dev: torch.Tensor,
+               token: torch.Tensor) -> None:
+        """Sample position pos_dev + 1 into ``seq``, ``pads`` and the (B,)
+        int64 ``token`` buffer the next step reads."""
+        OF.decode_sample(logits, pos_dev, self.seed, self.seq, self.lens,
+                         self.pads, token, self.top_k, self.greedy)
+
+
 class GraphedDecodeStep:
     """hipGraph-captured decode step (TODO.md "Serving"; VERDICT r1 item
     6): one replay = forward_step_static + in-graph pos_dev increment
@@ -347,11 +387,20 @@ class GraphedDecodeStep:
         for _ in range(n):
             logits = g.step(tokens)        # (B, V) device tensor
             tokens = <sample on host>      # no device kernels!
+
+    With a ``sampler`` (``DeviceSampler``) the capture also holds
+    ``OF.decode_sample``, after the forward and before the position
+    advance, writing into the step's own static ``token`` buffer: a replay
+    then feeds the next one and ``replay(n)`` runs n steps with nothing
+    from the host in between. The kernel is inside the graph, so the
+    pure-replay rule holds. Set the first token with
+    ``g.token.copy_(host_tokens)`` (a memcpy).
     """
 
     def __init__(self, model: ProGenBase, cache: DecodeCache,
                  start_pos: int, warmup: int = 2, fused: bool = False,
-                 fused_linear: bool = False):
+                 fused_linear: bool = False,
+                 sampler: Optional["DeviceSampler"] = None):
         _check_fused_linear(fused, fused_linear)
         dev = next(model.parameters()).device
         batch = cache.attn_prev[0].shape[0]
@@ -372,11 +421,23 @@ class GraphedDecodeStep:
         else:
             step_fn = forward_step_static
         self.cache = cache
+        self.sampler = sampler
         self.token = torch.zeros(batch, dtype=torch.long, device=dev)
         self.pos_dev = torch.tensor(start_pos, dtype=torch.long, device=dev)
+        if sampler is not None:
+            forward_fn = step_fn
 
-        # warmup + capture perturb the cache and pos; snapshot & restore
+            def step_fn(model, token, cache, pos_dev):
+                logits = forward_fn(model, token, cache, pos_dev)
+                sampler.sample(logits, pos_dev, token)
+                return logits
+
+        # warmup + capture perturb the cache and pos — and, with a sampler,
+        # seq, pads and the token buffer; snapshot & restore
+        sampled = [] if sampler is None else \
+            [sampler.seq, sampler.pads, self.token]
         snap = {
+            "sampled": [t.clone() for t in sampled],
             "k": [t.clone() for t in cache.k],
             "v": [t.clone() for t in cache.v],
             "ap": [t.clone() for t in cache.attn_prev],
@@ -413,6 +474,8 @@ class GraphedDecodeStep:
             gh = [t for t in cache.gate_hist if t is not None]
             for dst, src in zip(gh, snap["gh"]):
                 dst.copy_(src)
+            for dst, src in zip(sampled, snap["sampled"]):
+                dst.copy_(src)
             self.pos_dev.copy_(snap["pos"])
         torch.cuda.synchronize()
 
@@ -428,6 +491,21 @@ class GraphedDecodeStep:
         self.next_pos += 1
         self.cache.pos = self.next_pos
         return self.static_logits
+
+    def replay(self, n: int = 1) -> None:
+        """Replay ``n`` self-feeding steps back to back (needs a
+        ``sampler``): each reads the token the one before it sampled. No
+        host synchronisation and no copy in between. Raises IndexError,
+        without replaying, if that would pass seq_len."""
+        if self.sampler is None:
+            raise RuntimeError("replay() needs a GraphedDecodeStep built "
+                               "with a sampler; use step(tokens)")
+        if n < 0 or self.next_pos + n > self.seq_len:
+            raise IndexError(f"decode past seq_len ({self.seq_len})")
+        for _ in range(n):
+            self.graph.replay()
+        self.next_pos += n
+        self.cache.pos = self.next_pos
 
 
 def _check_fused_linear(fused: bool, fused_linear: bool) -> None:
@@ -453,6 +531,67 @@ def _eager_step(model: ProGenBase, token: torch.Tensor, cache: DecodeCache,
     return logits
 
 
+def _sample_batch_on_device(model: ProGenBase, seq: torch.Tensor, lens,
+                            top_k: Optional[int], seed: Optional[int], dev,
+                            graph: bool, fused: bool, fused_linear: bool,
+                            check_every: int) -> torch.Tensor:
+    """``sample_cached_batch`` with the sampler on the device: every step is
+    forward + ``OF.decode_sample`` + position increment, and the host only
+    looks at the pad counts every ``check_every`` steps. ``seq`` (B, length)
+    holds the primes, ``lens`` their lengths."""
+    if check_every < 1:
+        raise ValueError(f"check_every must be >= 1, got {check_every}")
+    dev = torch.device(dev)
+    B, length = seq.shape
+    if top_k is not None and seed is None:
+        # the host path would draw its noise from the global generator
+        seed = int(torch.randint(0, 2 ** 63 - 1, (1,)))
+    sampler = DeviceSampler(seq, lens, top_k, seed, dev)
+    cache = DecodeCache(model, batch=B, device=dev)
+    steps = length - 1
+    done = 0
+    if graph and dev.type == "cuda":
+        graphed = GraphedDecodeStep(model, cache, start_pos=0, fused=fused,
+                                    fused_linear=fused_linear,
+                                    sampler=sampler)
+        graphed.token.copy_(seq[:, 0].contiguous())  # H2D memcpy, no kernel
+
+        def run(n):
+            graphed.replay(n)
+    else:
+        token = seq[:, 0].contiguous().to(dev, copy=True)
+        pos_dev = torch.zeros((), dtype=torch.long).to(dev)
+
+        def run(n):
+            for _ in range(n):
+                if fused:
+                    # advances pos_dev itself, after the forward: sample
+                    # at the position the step ran at
+                    if cache.pos >= model.cfg.seq_len:
+                        raise IndexError(
+                            f"decode past seq_len ({model.cfg.seq_len})")
+                    logits = forward_step_fused(model, token, cache, pos_dev,
+                                                fused_linear=fused_linear)
+                    cache.pos += 1
+                else:
+                    # forward_step keeps its position on the host; the
+                    # sampler needs a device position of its own
+                    logits = forward_step(model, token, cache)
+                sampler.sample(logits, pos_dev, token)
+                pos_dev.add_(1)
+
+    while done < steps:
+        n = min(check_every, steps - done)
+        run(n)
+        done += n
+        if bool((sampler.pads.cpu() >= 2).all()):
+            break  # every row has emitted its EOS
+
+    out = sampler.seq.cpu()
+    remove_after_eos = (out == 0).long().cumsum(dim=-1) > 1
+    return out * (~remove_after_eos).long()
+
+
 @torch.no_grad()
 def sample_cached(
     model: ProGenBase,
@@ -465,6 +604,9 @@ def sample_cached(
     graph: bool = False,
     fused: bool = False,
     fused_linear: bool = False,
+    device_sampling: bool = False,
+    seed: Optional[int] = None,
+    check_every: int = 16,
 ) -> torch.Tensor:
     """Drop-in ``utils.sample`` with O(window + n_sgu) per-token cost.
 
@@ -476,8 +618,24 @@ def sample_cached(
     ``fused=True`` runs prefill and decode on ``forward_step_fused`` (the
     decode kernels on a GPU); combinable with ``graph``.
     ``fused_linear=True`` (needs ``fused``) also runs its projections on
-    the decode linear kernel."""
+    the decode linear kernel.
+
+    ``device_sampling=True`` is row 0 of ``sample_cached_batch`` with the
+    same flag, ``seed`` and ``check_every`` (see there); ``add_bos``
+    prepends a 0 to the prime."""
     _check_fused_linear(fused, fused_linear)
+    if device_sampling:
+        prime = torch.as_tensor(prime).long().flatten().cpu()
+        if add_bos:
+            prime = F.pad(prime, (1, 0))
+        return sample_cached_batch(
+            model, [prime], length, top_k=top_k, generator=generator,
+            device=device, graph=graph, fused=fused,
+            fused_linear=fused_linear, device_sampling=True, seed=seed,
+            check_every=check_every)[0]
+    if seed is not None:
+        raise ValueError("seed= keys the device sampler; without "
+                         "device_sampling=True pass generator=")
     dev = next(model.parameters()).device if device is None else device
     # the sequence and sampling math live on CPU (matching utils.sample's
     # generator semantics — its fn closure returns .cpu() logits); only
@@ -539,6 +697,9 @@ def sample_cached_batch(
     graph: bool = False,
     fused: bool = False,
     fused_linear: bool = False,
+    device_sampling: bool = False,
+    seed: Optional[int] = None,
+    check_every: int = 16,
 ) -> torch.Tensor:
     """Batched incremental decode: one forward_step advances ALL rows
     (the per-layer caches are batch-first), so serving throughput scales
@@ -555,7 +716,20 @@ def sample_cached_batch(
     (tests/test_decode.py::test_sample_cached_batch_greedy_parity).
     ``fused=True`` steps with ``forward_step_fused``; combinable with
     ``graph``. ``fused_linear=True`` (needs ``fused``) also runs its
-    projections on the decode linear kernel."""
+    projections on the decode linear kernel.
+
+    ``device_sampling=True`` keeps the sequences, the pad counts and the
+    token on the device and samples there (``OF.decode_sample``: the HIP
+    kernel on a GPU, inside the captured step with ``graph``; the reference
+    on the CPU). The host neither downloads logits nor uploads tokens: it
+    downloads the pad counts after every ``check_every`` steps to see
+    whether every row has finished, and the sequences once at the end.
+    Tokens emitted past a row's second pad are zeroed by the final rule, so
+    the result does not depend on ``check_every``. ``seed`` (an int in
+    [0, 2^63)) keys the sampler's Philox stream, which is its own and not
+    torch's: ``generator`` is refused. ``top_k=None`` with ``seed=None`` is
+    greedy and equals the host path's greedy output; ``top_k`` without a
+    seed draws one from torch's global generator on the host."""
     _check_fused_linear(fused, fused_linear)
     dev = next(model.parameters()).device if device is None else device
     primes = [torch.as_tensor(p).long().flatten().cpu() for p in primes]
@@ -564,6 +738,17 @@ def sample_cached_batch(
     seq = torch.zeros(B, length, dtype=torch.long)
     for i, p in enumerate(primes):
         seq[i, :lens[i]] = p
+    if device_sampling:
+        if generator is not None:
+            raise ValueError(
+                "device_sampling=True draws from the sampler's own Philox "
+                "stream, keyed by seed=; generator= cannot drive it")
+        return _sample_batch_on_device(model, seq, lens, top_k, seed, dev,
+                                       graph, fused, fused_linear,
+                                       check_every)
+    if seed is not None:
+        raise ValueError("seed= keys the device sampler; without "
+                         "device_sampling=True pass generator=")
 
     cache = DecodeCache(model, batch=B, device=dev)
     graphed = GraphedDecodeStep(model, cache, start_pos=0, fused=fused,

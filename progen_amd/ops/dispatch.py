@@ -134,6 +134,46 @@ def has_ext_decode_linear() -> bool:
     return _EXT_DECODE_LINEAR is not None
 
 
+# the decode step's sampler: a fourth module
+# (progen_amd._C_decode_sample, ops/hip/decode_sample_bindings.cpp)
+_EXT_DECODE_SAMPLE: Optional[Any] = None
+_EXT_DECODE_SAMPLE_ERR: Optional[str] = None
+_TRIED_DECODE_SAMPLE = False
+
+
+def _try_load_decode_sample() -> None:
+    global _EXT_DECODE_SAMPLE, _EXT_DECODE_SAMPLE_ERR, _TRIED_DECODE_SAMPLE
+    if _TRIED_DECODE_SAMPLE:
+        return
+    _TRIED_DECODE_SAMPLE = True
+    try:
+        _EXT_DECODE_SAMPLE = importlib.import_module(
+            "progen_amd._C_decode_sample")
+    except Exception as e:  # noqa: BLE001 - record and re-raise on GPU use
+        _EXT_DECODE_SAMPLE = None
+        _EXT_DECODE_SAMPLE_ERR = f"{type(e).__name__}: {e}"
+
+
+def ext_decode_sample() -> Any:
+    """Return the loaded decode-sample extension, raising loudly if
+    unavailable — device sampling never falls back to the host sampler."""
+    _try_load_decode_sample()
+    if _EXT_DECODE_SAMPLE is None:
+        raise RuntimeError(
+            "progen_amd decode-sample extension "
+            "(progen_amd._C_decode_sample) is not available (import error: "
+            f"{_EXT_DECODE_SAMPLE_ERR}). Build it in-tree with "
+            "`python setup.py build_ext --inplace` "
+            "(PYTORCH_ROCM_ARCH=gfx950)."
+        )
+    return _EXT_DECODE_SAMPLE
+
+
+def has_ext_decode_sample() -> bool:
+    _try_load_decode_sample()
+    return _EXT_DECODE_SAMPLE is not None
+
+
 def use_hip(t, op: str = None) -> bool:
     """True when tensor t lives on a ROCm GPU (→ HIP kernels are mandatory).
 
@@ -143,7 +183,7 @@ def use_hip(t, op: str = None) -> bool:
       the per-kernel bisect lever for the graphed-replay investigation
       (profiles/r02_graphed_nan_investigation.md). Tags: ln, attn, glu,
       sgu, ce, adamw; the fused decode step's ops are dec_ln, dec_attn,
-      dec_sgu and dec_linear.
+      dec_sgu, dec_linear and dec_sample.
     """
     if not t.is_cuda:
         return False

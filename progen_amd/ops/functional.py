@@ -400,3 +400,30 @@ def decode_linear(x: torch.Tensor, w: torch.Tensor, bias=None,
     if act == "gelu":
         return gelu(h)
     return h
+
+
+# ---------------------------------------------------------------------------
+# decode-step sampler (progen_amd._C_decode_sample)
+# ---------------------------------------------------------------------------
+
+# the kernel stages a whole row per workgroup (ops/hip/decode_sample_kernels.h)
+DEC_SAMPLE_MAX_V = 1024
+
+
+def decode_sample(logits: torch.Tensor, pos: torch.Tensor, seed: torch.Tensor,
+                  seq: torch.Tensor, lens: torch.Tensor, pads: torch.Tensor,
+                  token: torch.Tensor, top_k: int = 0, greedy: bool = False,
+                  u_out=None) -> None:
+    """Sample position pos + 1 of every row into ``seq``, ``pads`` and
+    ``token``, in place (reference.decode_sample): argmax when ``greedy``,
+    else gumbel-max over the strict top-k (``top_k`` 0: the whole row) with
+    Philox noise keyed by ``seed``. On a GPU this is the HIP kernel, which a
+    graph can capture; a vocabulary it does not serve is an error there,
+    never a fall-back."""
+    if dispatch.use_hip(logits, "dec_sample"):
+        dispatch.ext_decode_sample().dec_sample(
+            logits, pos, seed, seq, lens, pads, token, int(top_k),
+            bool(greedy), u_out)
+        return
+    reference.decode_sample(logits, pos, seed, seq, lens, pads, token,
+                            top_k, greedy, u_out)

@@ -410,3 +410,118 @@ def decode_linear(x: torch.Tensor, w: torch.Tensor, bias, act: str = "none"
     if act != "none":
         raise ValueError(f"decode_linear: unknown act {act!r}")
     return h
+
+
+# ---------------------------------------------------------------------------
+# decode-step sampler (ops/hip/decode_sample.hip)
+# ---------------------------------------------------------------------------
+# The device sampler draws its uniforms from Philox4x32-10, a stateless
+# counter-based generator: a replayed graph needs no generator state. This
+# stream is the sampler's own — it is NOT torch's generator stream.
+
+PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 on numpy arrays: ``counter`` (..., 4) and ``key``
+    (..., 2) hold 32-bit words; returns the (..., 4) output words as uint64.
+    Exact integer arithmetic: every product of two 32-bit words fits in
+    uint64."""
+    import numpy as np
+    m32 = np.uint64(0xFFFFFFFF)
+    c = [np.asarray(counter, dtype=np.uint64)[..., i] & m32 for i in range(4)]
+    k = [np.asarray(key, dtype=np.uint64)[..., i] & m32 for i in range(2)]
+    for _ in range(10):
+        p0 = np.uint64(PHILOX_M0) * c[0]
+        p1 = np.uint64(PHILOX_M1) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k[0], p1 & m32,
+             (p0 >> np.uint64(32)) ^ c[3] ^ k[1], p0 & m32]
+        k = [(k[0] + np.uint64(PHILOX_W0)) & m32,
+             (k[1] + np.uint64(PHILOX_W1)) & m32]
+    return np.stack(np.broadcast_arrays(*c), axis=-1)
+
+
+def decode_sample_uniform(seed: int, w: int, B: int, V: int) -> torch.Tensor:
+    """The sampler's uniforms for position ``w``: (B, V) fp32 in [0, 1).
+    Key = (seed & 0xffffffff, seed >> 32), counter = (j, w, b, 0); output
+    word i of block j belongs to vocabulary index 4j + i; u = (x >> 8) *
+    2^-24, exact in fp32."""
+    import numpy as np
+    nblk = -(-V // 4)
+    ctr = np.zeros((B, nblk, 4), dtype=np.uint64)
+    ctr[..., 0] = np.arange(nblk, dtype=np.uint64)[None, :]
+    ctr[..., 1] = np.uint64(w)
+    ctr[..., 2] = np.arange(B, dtype=np.uint64)[:, None]
+    key = np.array([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF],
+                   dtype=np.uint64)
+    x = philox4x32_10(ctr, key).reshape(B, nblk * 4)[:, :V]
+    u = (x >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    return torch.from_numpy(u)
+
+
+def decode_sample_scores(t: torch.Tensor, u: Optional[torch.Tensor],
+                         top_k: int, greedy: bool) -> torch.Tensor:
+    """The (B, V) fp32 scores whose first argmax is the sampled token.
+    Greedy: the logits. Else t + g with g = -log(-log(u + 1e-20) + 1e-20)
+    in fp32; with ``top_k`` > 0 only entries with fewer than ``top_k``
+    entries >= them (select_top_k's strict > the k-th largest value) keep
+    their score, every other entry scores exactly 0."""
+    t = t.float()
+    if greedy:
+        return t
+    eps = 1e-20
+    g = -torch.log(-torch.log(u.float() + eps) + eps)
+    if top_k <= 0:
+        return t + g
+    rank = (t.unsqueeze(1) >= t.unsqueeze(2)).sum(dim=-1)  # #{i: t_i >= t_j}
+    sel = rank < top_k
+    zero = torch.zeros_like(t)
+    return torch.where(sel, t, zero) + torch.where(sel, g, zero)
+
+
+def decode_sample(
+    logits: torch.Tensor,
+    pos: torch.Tensor,
+    seed: torch.Tensor,
+    seq: torch.Tensor,
+    lens: torch.Tensor,
+    pads: torch.Tensor,
+    token: torch.Tensor,
+    top_k: int = 0,
+    greedy: bool = False,
+    u_out: Optional[torch.Tensor] = None,
+) -> None:
+    """Sample position w = pos + 1 of every row, in place.
+
+    logits (B, V); pos 0-dim int64; seed (1,) int64; seq (B, L), lens, pads
+    and token (B,) int64. Row b's token is the first argmax of
+    ``decode_sample_scores`` with the uniforms of ``decode_sample_uniform``;
+    it is written to seq[b, w] unless the prime covers w (w < lens[b]); then
+    pads[b] += (seq[b, w] == 0) and token[b] = seq[b, w]. ``u_out`` (B, V)
+    fp32 receives the uniforms. With pos < 0 or w >= L nothing is touched.
+
+    Goes through the host (the position and the seed are read there, and
+    Philox runs in numpy), so it cannot be captured in a graph."""
+    if logits.is_cuda and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(
+            "decode_sample: the reference sampler reads the position on the "
+            "host and cannot be captured in a graph; capture needs the HIP "
+            "kernel (do not list dec_sample in PROGEN_EAGER_OPS)")
+    B, V = logits.shape
+    L = seq.shape[1]
+    p = int(pos)
+    w = p + 1
+    if p < 0 or w >= L:
+        return
+    u = None
+    if not greedy:
+        u = decode_sample_uniform(int(seed[0]), w, B, V)
+        if u_out is not None:
+            u_out.copy_(u)
+    scores = decode_sample_scores(logits.detach().cpu(), u, int(top_k), greedy)
+    sampled = scores.argmax(dim=-1).to(seq.device)  # first maximal index
+    col = torch.where(lens <= w, sampled, seq[:, w])
+    seq[:, w] = col
+    pads.add_((col == 0).long())
+    token.copy_(col)

@@ -34,10 +34,16 @@ load_dotenv()  # reference: sample.py:1-2
 @click.option('--fused-linear', 'fused_linear', default=False, is_flag=True,
               help='with --fused: run the step\'s projections on the decode '
                    'linear kernel (bias and GLU/GELU folded in)')
+@click.option('--device-sampling', 'device_sampling', default=False,
+              is_flag=True,
+              help='with --cached: sample on the device, inside the step '
+                   '(--seed then keys the device sampler\'s own stream)')
 def main(seed, checkpoint_path, prime, fast, cached, graph, fused,
-         fused_linear):
+         fused_linear, device_sampling):
     if fused_linear and not fused:
         raise click.UsageError('--fused-linear needs --fused')
+    if device_sampling and not cached:
+        raise click.UsageError('--device-sampling needs --cached')
     from progen_amd.tuning import enable_tuned_gemms
     enable_tuned_gemms()
     _, get_last_checkpoint, _ = get_checkpoint_fns(checkpoint_path)
@@ -79,9 +85,11 @@ def main(seed, checkpoint_path, prime, fast, cached, graph, fused,
 
     if cached:
         from progen_amd.decode import sample_cached
+        sampling = dict(device_sampling=True, seed=seed) if device_sampling \
+            else dict(generator=g)
         sampled = sample_cached(module, prime_tensor, seq_len, top_k=25,
-                                add_bos=True, generator=g, graph=graph,
-                                fused=fused, fused_linear=fused_linear)
+                                add_bos=True, graph=graph, fused=fused,
+                                fused_linear=fused_linear, **sampling)
     elif fast:
         sampled = sample_fast(fwd, prime_tensor, seq_len, top_k=25,
                               add_bos=True, generator=g,

@@ -15,7 +15,9 @@ Endpoints:
     POST /generate           {"primes": [str] (or "prime": str),
                               "num_tokens": int <= seq_len (default seq_len),
                               "top_k": int (default 25; 0/null = greedy),
-                              "seed": int (optional, deterministic sampling)}
+                              "seed": int (optional, deterministic sampling;
+                                      with --device-sampling it keys the
+                                      device sampler's own stream)}
                              -> {"sequences": [str], "tokens": [[int]],
                                  "ms": float}
 
@@ -45,6 +47,7 @@ from progen_amd.utils import load_dotenv
 def create_app(module: ProGenBase, cfg: ProGenConfig, *,
                graph: bool = False, fused: bool = False,
                fused_linear: bool = False,
+               device_sampling: bool = False,
                meta: Optional[dict] = None):
     """Build the FastAPI app around a ready (device-placed, eval) module."""
     if fused_linear and not fused:
@@ -63,6 +66,7 @@ def create_app(module: ProGenBase, cfg: ProGenConfig, *,
         "graph": bool(graph and device.type == "cuda"),
         "fused": bool(fused),
         "fused_linear": bool(fused_linear),
+        "device_sampling": bool(device_sampling),
         **(meta or {}),
     }
 
@@ -101,14 +105,23 @@ def create_app(module: ProGenBase, cfg: ProGenConfig, *,
             if len(toks) + 1 >= length:
                 raise HTTPException(400, f"prime longer than num_tokens: {p!r}")
             rows.append(torch.tensor([0] + toks, dtype=torch.long))
-        gen = torch.Generator().manual_seed(req.seed) \
-            if req.seed is not None else None
+        if info["device_sampling"]:
+            # the request's seed keys the device sampler's own stream; a
+            # missing one is drawn on the host (inside the decoder)
+            if req.seed is not None and not 0 <= req.seed < 2 ** 63:
+                raise HTTPException(400, "seed must be in [0, 2^63)")
+            sampling = dict(device_sampling=True, seed=req.seed)
+        else:
+            sampling = dict(
+                generator=torch.Generator().manual_seed(req.seed)
+                if req.seed is not None else None)
         t0 = time.perf_counter()
         with lock, torch.no_grad():
             out = sample_cached_batch(module, rows, length, top_k=top_k,
-                                      generator=gen, graph=info["graph"],
+                                      graph=info["graph"],
                                       fused=info["fused"],
-                                      fused_linear=info["fused_linear"])
+                                      fused_linear=info["fused_linear"],
+                                      **sampling)
         ms = (time.perf_counter() - t0) * 1e3
         seqs, toks_out = [], []
         for row, prime_row in zip(out, rows):
@@ -157,7 +170,13 @@ def load_module(checkpoint_path: str):
 @click.option("--fused-linear", "fused_linear", default=False, is_flag=True,
               help="with --fused: run the step's projections on the decode "
                    "linear kernel (bias and GLU/GELU folded in)")
-def main(checkpoint_path, host, port, graph, fused, fused_linear):
+@click.option("--device-sampling", "device_sampling", default=False,
+              is_flag=True,
+              help="sample on the device, inside the step (with --graph: "
+                   "inside the captured graph); a request's seed then keys "
+                   "the device sampler's own stream")
+def main(checkpoint_path, host, port, graph, fused, fused_linear,
+         device_sampling):
     if fused_linear and not fused:
         raise click.UsageError("--fused-linear needs --fused")
     load_dotenv()
@@ -166,7 +185,8 @@ def main(checkpoint_path, host, port, graph, fused, fused_linear):
     import uvicorn
     module, cfg, meta = load_module(checkpoint_path)
     app = create_app(module, cfg, graph=graph, fused=fused,
-                     fused_linear=fused_linear, meta=meta)
+                     fused_linear=fused_linear,
+                     device_sampling=device_sampling, meta=meta)
     uvicorn.run(app, host=host, port=port, log_level="info")
 
 

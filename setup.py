@@ -1,5 +1,6 @@
-"""In-tree build of the progen_amd._C, progen_amd._C_decode and
-progen_amd._C_decode_linear HIP extensions (gfx950 only).
+"""In-tree build of the progen_amd._C, progen_amd._C_decode,
+progen_amd._C_decode_linear and progen_amd._C_decode_sample HIP extensions
+(gfx950 only).
 
     PYTORCH_ROCM_ARCH=gfx950 python setup.py build_ext --inplace
 
@@ -45,6 +46,12 @@ DECODE_LINEAR_SOURCES = [
     "progen_amd/ops/hip/decode_linear.hip",
 ]
 
+# the decode step's sampler; a fourth module for the same reason
+DECODE_SAMPLE_SOURCES = [
+    "progen_amd/ops/hip/decode_sample_bindings.cpp",
+    "progen_amd/ops/hip/decode_sample.hip",
+]
+
 COMPILE_ARGS = {
     "cxx": ["-O3", "-std=c++17"],
     "nvcc": ["-O3", "-std=c++17"],
@@ -66,6 +73,11 @@ setup(
         CUDAExtension(
             name="progen_amd._C_decode_linear",
             sources=DECODE_LINEAR_SOURCES,
+            extra_compile_args=COMPILE_ARGS,
+        ),
+        CUDAExtension(
+            name="progen_amd._C_decode_sample",
+            sources=DECODE_SAMPLE_SOURCES,
             extra_compile_args=COMPILE_ARGS,
         ),
     ],

@@ -7,9 +7,13 @@ weak #8).
 Modes: eager per-token step, hipGraph-captured step (--graph), batched
 (--batch N), fused decode kernels (--fused, with or without --graph),
 and on top of --fused the decode linear kernel (--fused-linear).
+Sampling: on the host (the default: logits down, token up, every step) or
+on the device (--device-sampling: the sampler runs in the step, the host
+downloads the pad counts every --check-every steps); greedy, or top-k
+gumbel-max with --top-k K in either arm.
 Serving metric: ms/token (batch 1) and tokens/s aggregate.
 
-Usage (GPU box):  python tools/bench_decode.py [--tokens 128] [--graph] [--fused [--fused-linear]] [--batch 8]
+Usage (GPU box):  python tools/bench_decode.py [--tokens 128] [--graph] [--fused [--fused-linear]] [--batch 8] [--device-sampling] [--top-k 25]
 """
 
 import argparse
@@ -23,8 +27,9 @@ import torch
 
 from progen_amd import ProGenBase
 from progen_amd.config import ProGenConfig
-from progen_amd.decode import (DecodeCache, GraphedDecodeStep, forward_step,
-                               forward_step_fused)
+from progen_amd.decode import (DecodeCache, DeviceSampler, GraphedDecodeStep,
+                               forward_step, forward_step_fused)
+from progen_amd.ops import reference as R
 
 
 def parse_args(argv=None):
@@ -38,10 +43,33 @@ def parse_args(argv=None):
     ap.add_argument("--fused-linear", action="store_true",
                     help="with --fused: projections on the decode linear "
                          "kernel")
+    ap.add_argument("--device-sampling", action="store_true",
+                    help="sample in the step, on the device; the host only "
+                         "downloads the pad counts")
+    ap.add_argument("--top-k", type=int, default=0,
+                    help="top-k gumbel-max sampling in either arm "
+                         "(0: greedy argmax)")
+    ap.add_argument("--check-every", type=int, default=16,
+                    help="with --device-sampling: steps between pad-count "
+                         "downloads")
+    ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args(argv)
     if args.fused_linear and not args.fused:
         ap.error("--fused-linear needs --fused")
+    if args.top_k < 0 or args.check_every < 1:
+        ap.error("--top-k must be >= 0 and --check-every >= 1")
     return args
+
+
+def host_sample(logits, top_k, gen):
+    """The host arm's sampler, as decode.sample_cached_batch runs it: the
+    logits come down, no device kernel runs."""
+    rows = logits.cpu().float()
+    if not top_k:
+        return rows.argmax(dim=-1)
+    noise = R.gumbel_noise(rows.shape, generator=gen)
+    mask, rows = R.select_top_k(rows, top_k)
+    return (rows + noise * mask).argmax(dim=-1)
 
 
 def flagship():
@@ -61,8 +89,11 @@ def run(m, args):
     B = args.batch
     cache = DecodeCache(m, batch=B)
     tok = torch.randint(1, 256, (B,), device="cuda")
+    gen = torch.Generator().manual_seed(args.seed)
 
-    if args.graph:
+    if args.device_sampling:
+        mode, t0 = _run_device_sampling(m, args, cache, tok)
+    elif args.graph:
         # a couple of eager steps as prefill, then capture
         for _ in range(2):
             logits = forward_step(m, tok, cache)
@@ -72,15 +103,15 @@ def run(m, args):
                               fused=args.fused,
                               fused_linear=args.fused_linear)
         # pure-replay rule: sampling runs on the HOST (memcpys only
-        # between replays — a device argmax kernel would poison replay)
+        # between replays — an eager device argmax kernel between them
+        # would poison replay; --device-sampling puts the sampler INSIDE
+        # the graph instead)
         for _ in range(args.warmup):
-            logits = g.step(tok)
-            tok = logits.cpu().float().argmax(dim=-1)
+            tok = host_sample(g.step(tok), args.top_k, gen)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.tokens):
-            logits = g.step(tok)
-            tok = logits.cpu().float().argmax(dim=-1)
+            tok = host_sample(g.step(tok), args.top_k, gen)
         torch.cuda.synchronize()
         mode = "graphed"
     else:
@@ -96,24 +127,89 @@ def run(m, args):
         else:
             def step(tok):
                 return forward_step(m, tok, cache)
+        if args.top_k:
+            def pick(logits):
+                return host_sample(logits, args.top_k, gen).cuda()
+        else:
+            def pick(logits):
+                return logits.argmax(dim=-1)
         for _ in range(args.warmup):
-            tok = step(tok).argmax(dim=-1)
+            tok = pick(step(tok))
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.tokens):
-            tok = step(tok).argmax(dim=-1)
+            tok = pick(step(tok))
         torch.cuda.synchronize()
         mode = "eager"
     if args.fused:
         mode += "+fused"
     if args.fused_linear:
         mode += "+linear"
+    if args.device_sampling:
+        mode += f"+devsample/{args.check_every}"
+    if args.top_k:
+        mode += f"+top{args.top_k}"
     dt = time.perf_counter() - t0
     n = args.tokens * B
     print(f"decode[{mode}, batch {B}]: {args.tokens} steps in {dt:.3f}s -> "
           f"{n / dt:.1f} tok/s aggregate, {1e3 * dt / args.tokens:.2f} ms/step "
           f"(ProGen-1.2B flagship config, bf16, cached)")
     return 1e3 * dt / args.tokens
+
+
+def _run_device_sampling(m, args, cache, tok):
+    """The --device-sampling arm: warm-up and timed steps with the sampler
+    in the step; returns (mode, t0) with the clock started after warm-up.
+    Rows never finish early here (the loop is timed to --tokens steps
+    whatever is sampled): the pad counts are downloaded, not acted on."""
+    B = args.batch
+    total = args.warmup + args.tokens
+    if 2 + total >= m.cfg.seq_len:
+        raise SystemExit("--warmup + --tokens must stay below seq_len - 2")
+    seq = torch.zeros(B, m.cfg.seq_len, dtype=torch.long)
+    for p in range(2):  # a couple of eager steps as prefill
+        seq[:, p] = tok.cpu()
+        tok = forward_step(m, tok, cache).argmax(dim=-1)
+    seq[:, 2] = tok.cpu()
+    sampler = DeviceSampler(seq, [3] * B, args.top_k or None,
+                            args.seed if args.top_k else None, "cuda")
+    if args.graph:
+        g = GraphedDecodeStep(m, cache, start_pos=cache.pos, fused=args.fused,
+                              fused_linear=args.fused_linear, sampler=sampler)
+        g.token.copy_(tok.cpu())
+        run_steps = g.replay
+        mode = "graphed"
+    else:
+        token = tok.clone()
+        pos_dev = torch.full((), cache.pos, dtype=torch.long, device="cuda")
+
+        def run_steps(n):
+            for _ in range(n):
+                if args.fused:
+                    logits = forward_step_fused(
+                        m, token, cache, pos_dev,
+                        fused_linear=args.fused_linear)
+                    cache.pos += 1
+                else:
+                    logits = forward_step(m, token, cache)
+                sampler.sample(logits, pos_dev, token)
+                pos_dev.add_(1)
+        mode = "eager"
+
+    def chunks(n):
+        done = 0
+        while done < n:
+            c = min(args.check_every, n - done)
+            run_steps(c)
+            done += c
+            sampler.pads.cpu()  # the loop's only download
+
+    chunks(args.warmup)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    chunks(args.tokens)
+    torch.cuda.synchronize()
+    return mode, t0
 
 
 def main():
