@@ -21,6 +21,7 @@ with zeros-not-inf, gumbel-max, zero-after-second-pad).
 
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import torch
@@ -325,6 +326,156 @@ def forward_step_fused(model: ProGenBase, token: torch.Tensor,
     return linear(y, model.to_logits)
 
 
+# shortest prime the callers route to ``prefill`` on a GPU, from the
+# time-to-first-token measurement of profiles/decode_prefill.md: on the
+# flagship the forward loses to the step loop at 2 and 3 tokens, ties at 4
+# and wins from 7 (batch 8) and 8 (batch 1)
+PREFILL_MIN_TOKENS = 8
+
+
+def _prefill_len(model: ProGenBase, P: int, device) -> int:
+    """Rows of the forward that prefills P positions: P padded up to what
+    the full-sequence ops take. The reference ops want whole windows;
+    the GPU's ``sgu_fwd`` also wants multiples of 256 rows."""
+    L = model.cfg.window_size
+    if torch.device(device).type == "cuda" and \
+            any(ff.sgu is not None for _attn, ff in model.layers):
+        L = math.lcm(L, 256)
+    return -(-P // L) * L
+
+
+def prefill_supported(model: ProGenBase, P: int, device) -> bool:
+    """True when the samplers prefill a P-token prime on ``device`` with one
+    forward (``prefill``) instead of P decode steps. On the CPU that is
+    whenever the padded prime fits the model; on a GPU it also takes what
+    the kernels serve (bf16, dim_head 64, window and SGU width multiples of
+    64) and a prime of at least ``PREFILL_MIN_TOKENS``."""
+    cfg = model.cfg
+    device = torch.device(device)
+    if not 1 <= P <= cfg.seq_len or \
+            _prefill_len(model, P, device) > cfg.seq_len:
+        return False
+    if device.type != "cuda":
+        return True
+    return next(model.parameters()).dtype == torch.bfloat16 \
+        and cfg.dim_head == 64 and cfg.window_size % 64 == 0 \
+        and all(ff.sgu is None or ff.sgu.norm_weight.shape[0] % 64 == 0
+                for _attn, ff in model.layers) \
+        and P >= PREFILL_MIN_TOKENS
+
+
+@torch.no_grad()
+def prefill(model: ProGenBase, tokens: torch.Tensor, cache: DecodeCache,
+            pos_dev: Optional[torch.Tensor] = None,
+            want_logits: bool = False) -> Optional[torch.Tensor]:
+    """Fill a fresh ``cache`` for positions [0, P) from ONE forward over the
+    (B, P) ``tokens``, instead of P decode steps that each stream every
+    weight for a single row.
+
+    The model is causal, so row p of a full forward equals what step p
+    computes; the tokens are padded with id 0 to the length the
+    full-sequence ops take and rows < P are exact. The layer loop is
+    ``ProGenBase.forward``'s, with ``OF.prefill_attention`` and
+    ``OF.prefill_sgu`` leaving the rotated k/v and the LN'd gate rows in
+    the cache on their way, and plain ``F.linear`` projections as in the
+    decode steps. The token-shift halos ``attn_prev``/``ff_prev`` get the
+    unshifted LN of row P-1. Cache rows >= P are not touched.
+
+    Afterwards ``cache.pos`` is P, as is ``pos_dev`` (the fused step's
+    0-dim int64 device position) when given. ``want_logits``: return the
+    (B, V) logits of row P-1, which is all a sampler needs; the final norm
+    and the head are skipped for every other row. Eager, so it belongs
+    before any graph capture.
+
+    Raises ValueError unless ``tokens`` is (B, P >= 1) for the cache's batch
+    and the cache is fresh, IndexError when the padded prime does not fit
+    the model's seq_len."""
+    cfg = model.cfg
+    tokens = torch.as_tensor(tokens)
+    if tokens.dim() != 2 or tokens.shape[1] < 1 \
+            or tokens.shape[0] != cache.attn_prev[0].shape[0]:
+        raise ValueError("prefill: tokens must be (B, P >= 1) with the "
+                         f"cache's batch, got {tuple(tokens.shape)}")
+    if cache.pos != 0:
+        raise ValueError("prefill needs a fresh cache, this one is at "
+                         f"position {cache.pos}")
+    P = tokens.shape[1]
+    dev = cache.attn_prev[0].device
+    Np = _prefill_len(model, P, dev)
+    if Np > cfg.seq_len:
+        raise IndexError(f"prefill of {P} tokens ({Np} padded) past seq_len "
+                         f"({cfg.seq_len})")
+    if model.rotary_sin.dtype != torch.float32:
+        sin, cos = R.fixed_pos_embedding(cfg.seq_len, cfg.dim_head,
+                                         device=model.rotary_sin.device)
+        model.rotary_sin, model.rotary_cos = sin, cos
+    sin, cos = model.rotary_sin, model.rotary_cos
+    last = P - 1
+
+    def halo(s, weight, prev):
+        # the decode step's own LN of one row, which also stores it
+        return OF.decode_ln_shift(s[:, last].contiguous(), None, weight, prev,
+                                  shift=False)
+
+    h = model.embed(F.pad(tokens.long(), (0, Np - P)).to(dev))  # (B, Np, dim)
+    r = None
+    for li, (attn, ff) in enumerate(model.layers):
+        y, h = OF.ln_shift_res(h, r, attn.norm_weight,
+                               shift=attn.shift_tokens)
+        halo(h, attn.norm_weight, cache.attn_prev[li])
+        qkv = F.linear(y, attn.to_qkv.weight)
+        out = OF.prefill_attention(qkv, sin, cos, attn.heads,
+                                   attn.window_size, cache.k[li],
+                                   cache.v[li], P)
+        a = F.linear(out, attn.to_out.weight, attn.to_out.bias)
+
+        y, h = OF.ln_shift_res(h, a, ff.norm_weight, shift=ff.shift_tokens)
+        halo(h, ff.norm_weight, cache.ff_prev[li])
+        t = F.linear(y, ff.proj_in.weight, ff.proj_in.bias)
+        t = OF.glu_gelu(t) if ff.glu else OF.gelu(t)
+        if ff.sgu is not None:
+            sgu = ff.sgu
+            t = OF.prefill_sgu(t, sgu.norm_weight, sgu.spatial_weights,
+                               sgu.spatial_biases, cache.gate_hist[li], P)
+            t = F.linear(t, sgu.proj_out.weight, sgu.proj_out.bias)
+        r = F.linear(t, ff.proj_out.weight, ff.proj_out.bias)
+
+    cache.pos = P
+    if pos_dev is not None:
+        pos_dev.fill_(P)
+    if not want_logits:
+        return None
+    y = OF.decode_ln_shift(h[:, last].contiguous(), r[:, last].contiguous(),
+                           model.final_norm_weight, None, shift=False)
+    return F.linear(y, model.to_logits.weight, model.to_logits.bias)
+
+
+def _prefill_if_supported(model: ProGenBase, tokens: torch.Tensor,
+                          cache: DecodeCache, pos_dev: Optional[torch.Tensor],
+                          want_logits: bool):
+    """``prefill`` for the samplers: (True, its result) when
+    ``prefill_supported``, else (False, None) and the caller steps through
+    the tokens as it would without the flag."""
+    dev = cache.attn_prev[0].device
+    if tokens.shape[1] < 1 or \
+            not prefill_supported(model, tokens.shape[1], dev):
+        return False, None
+    return True, prefill(model, tokens, cache, pos_dev, want_logits)
+
+
+def _prefill_common_prefix(model: ProGenBase, seq: torch.Tensor, lens,
+                           cache: DecodeCache) -> int:
+    """Prefill what every row of a ragged batch has in common: the rows of a
+    cache share one position, so that is the first min(lens) - 1 columns of
+    ``seq`` (B, length) — every row's next token is then still a prime
+    token, and no logits are needed. Returns the position to step on from:
+    that count, or 0 when nothing was prefilled."""
+    Pc = min(lens) - 1
+    done, _ = _prefill_if_supported(model, seq[:, :max(Pc, 0)], cache, None,
+                                    False)
+    return Pc if done else 0
+
+
 class DeviceSampler:
     """Sampling state that lives on the model's device, for
     ``OF.decode_sample``: the sequences ``seq`` (B, L), the prime lengths
@@ -336,10 +487,12 @@ class DeviceSampler:
     the pure-replay rule. ``top_k`` None is no top-k mask; ``seed`` None is
     greedy argmax, else an int in [0, 2^63). The uniform stream is the
     kernel's own Philox4x32-10 (ops/reference.py, decode_sample_uniform),
-    not torch's generator stream."""
+    not torch's generator stream. ``written``: how many leading positions
+    of ``seq`` are already decided when sampling starts (1, or more after
+    a prefill); the pad counts start from those."""
 
     def __init__(self, seq: torch.Tensor, lens, top_k: Optional[int],
-                 seed: Optional[int], device):
+                 seed: Optional[int], device, written: int = 1):
         seq = torch.as_tensor(seq).long().cpu()
         if seq.dim() != 2:
             raise ValueError("DeviceSampler: seq must be (B, L)")
@@ -352,8 +505,9 @@ class DeviceSampler:
         self.seq = seq.contiguous().to(device, copy=True)  # never the caller's
         self.lens = torch.tensor([int(n) for n in lens],
                                  dtype=torch.long).to(device)
-        # position 0 is written at entry; the unfilled tail must not count
-        self.pads = (seq[:, 0] == 0).long().to(device)
+        # the first ``written`` positions are written at entry; the unfilled
+        # tail must not count
+        self.pads = (seq[:, :written] == 0).sum(dim=-1).to(device)
         self.seed = torch.tensor([0 if seed is None else int(seed)],
                                  dtype=torch.long).to(device)
 
@@ -534,11 +688,13 @@ def _eager_step(model: ProGenBase, token: torch.Tensor, cache: DecodeCache,
 def _sample_batch_on_device(model: ProGenBase, seq: torch.Tensor, lens,
                             top_k: Optional[int], seed: Optional[int], dev,
                             graph: bool, fused: bool, fused_linear: bool,
-                            check_every: int) -> torch.Tensor:
+                            check_every: int,
+                            prefill: bool = False) -> torch.Tensor:
     """``sample_cached_batch`` with the sampler on the device: every step is
     forward + ``OF.decode_sample`` + position increment, and the host only
     looks at the pad counts every ``check_every`` steps. ``seq`` (B, length)
-    holds the primes, ``lens`` their lengths."""
+    holds the primes, ``lens`` their lengths. ``prefill``: as in
+    ``sample_cached_batch``."""
     if check_every < 1:
         raise ValueError(f"check_every must be >= 1, got {check_every}")
     dev = torch.device(dev)
@@ -546,21 +702,23 @@ def _sample_batch_on_device(model: ProGenBase, seq: torch.Tensor, lens,
     if top_k is not None and seed is None:
         # the host path would draw its noise from the global generator
         seed = int(torch.randint(0, 2 ** 63 - 1, (1,)))
-    sampler = DeviceSampler(seq, lens, top_k, seed, dev)
     cache = DecodeCache(model, batch=B, device=dev)
-    steps = length - 1
+    start = _prefill_common_prefix(model, seq, lens, cache) if prefill else 0
+    sampler = DeviceSampler(seq, lens, top_k, seed, dev, written=start + 1)
+    steps = length - 1 - start
     done = 0
     if graph and dev.type == "cuda":
-        graphed = GraphedDecodeStep(model, cache, start_pos=0, fused=fused,
-                                    fused_linear=fused_linear,
+        graphed = GraphedDecodeStep(model, cache, start_pos=start,
+                                    fused=fused, fused_linear=fused_linear,
                                     sampler=sampler)
-        graphed.token.copy_(seq[:, 0].contiguous())  # H2D memcpy, no kernel
+        # H2D memcpy, no kernel
+        graphed.token.copy_(seq[:, start].contiguous())
 
         def run(n):
             graphed.replay(n)
     else:
-        token = seq[:, 0].contiguous().to(dev, copy=True)
-        pos_dev = torch.zeros((), dtype=torch.long).to(dev)
+        token = seq[:, start].contiguous().to(dev, copy=True)
+        pos_dev = torch.full((), start, dtype=torch.long).to(dev)
 
         def run(n):
             for _ in range(n):
@@ -607,6 +765,7 @@ def sample_cached(
     device_sampling: bool = False,
     seed: Optional[int] = None,
     check_every: int = 16,
+    prefill: bool = False,
 ) -> torch.Tensor:
     """Drop-in ``utils.sample`` with O(window + n_sgu) per-token cost.
 
@@ -622,7 +781,11 @@ def sample_cached(
 
     ``device_sampling=True`` is row 0 of ``sample_cached_batch`` with the
     same flag, ``seed`` and ``check_every`` (see there); ``add_bos``
-    prepends a 0 to the prime."""
+    prepends a 0 to the prime.
+
+    ``prefill=True`` builds the cache of the prime with one forward over
+    all its tokens (``prefill``) instead of one decode step per token,
+    where ``prefill_supported``; elsewhere it changes nothing."""
     _check_fused_linear(fused, fused_linear)
     if device_sampling:
         prime = torch.as_tensor(prime).long().flatten().cpu()
@@ -632,7 +795,7 @@ def sample_cached(
             model, [prime], length, top_k=top_k, generator=generator,
             device=device, graph=graph, fused=fused,
             fused_linear=fused_linear, device_sampling=True, seed=seed,
-            check_every=check_every)[0]
+            check_every=check_every, prefill=prefill)[0]
     if seed is not None:
         raise ValueError("seed= keys the device sampler; without "
                          "device_sampling=True pass generator=")
@@ -650,7 +813,11 @@ def sample_cached(
     cache = DecodeCache(model, batch=1, device=dev)
     pos_dev = torch.zeros((), dtype=torch.long, device=dev) if fused else None
     logits = None
-    for p in range(start_pos):                           # prefill
+    done = False
+    if prefill:
+        done, logits = _prefill_if_supported(
+            model, seq[:start_pos].unsqueeze(0), cache, pos_dev, True)
+    for p in range(0 if done else start_pos):            # prefill by steps
         logits = _eager_step(model, seq[p:p + 1].to(dev), cache, pos_dev,
                              fused_linear)
 
@@ -700,6 +867,7 @@ def sample_cached_batch(
     device_sampling: bool = False,
     seed: Optional[int] = None,
     check_every: int = 16,
+    prefill: bool = False,
 ) -> torch.Tensor:
     """Batched incremental decode: one forward_step advances ALL rows
     (the per-layer caches are batch-first), so serving throughput scales
@@ -729,7 +897,12 @@ def sample_cached_batch(
     [0, 2^63)) keys the sampler's Philox stream, which is its own and not
     torch's: ``generator`` is refused. ``top_k=None`` with ``seed=None`` is
     greedy and equals the host path's greedy output; ``top_k`` without a
-    seed draws one from torch's global generator on the host."""
+    seed draws one from torch's global generator on the host.
+
+    ``prefill=True`` builds the cache of the primes' common prefix, their
+    first min(len) - 1 positions, with one forward (``prefill``) where
+    ``prefill_supported``, and steps on from there; the tokens are those
+    of the step loop up to fp reduction order."""
     _check_fused_linear(fused, fused_linear)
     dev = next(model.parameters()).device if device is None else device
     primes = [torch.as_tensor(p).long().flatten().cpu() for p in primes]
@@ -745,23 +918,24 @@ def sample_cached_batch(
                 "stream, keyed by seed=; generator= cannot drive it")
         return _sample_batch_on_device(model, seq, lens, top_k, seed, dev,
                                        graph, fused, fused_linear,
-                                       check_every)
+                                       check_every, prefill)
     if seed is not None:
         raise ValueError("seed= keys the device sampler; without "
                          "device_sampling=True pass generator=")
 
     cache = DecodeCache(model, batch=B, device=dev)
-    graphed = GraphedDecodeStep(model, cache, start_pos=0, fused=fused,
+    start = _prefill_common_prefix(model, seq, lens, cache) if prefill else 0
+    graphed = GraphedDecodeStep(model, cache, start_pos=start, fused=fused,
                                 fused_linear=fused_linear) \
         if (graph and dev.type == "cuda") else None
     # the graphed step owns its device position; the eager fused one needs one
-    pos_dev = torch.zeros((), dtype=torch.long, device=dev) \
+    pos_dev = torch.full((), start, dtype=torch.long, device=dev) \
         if (fused and graphed is None) else None
     greedy = top_k is None and generator is None
     # per-row pad counts over WRITTEN tokens only (the unfilled zero tail
-    # must not count as EOS); position 0 is written at entry
-    pads = [int(seq[i, 0] == 0) for i in range(B)]
-    for pos in range(length - 1):
+    # must not count as EOS); positions 0..start are written at entry
+    pads = [int((seq[i, :start + 1] == 0).sum()) for i in range(B)]
+    for pos in range(start, length - 1):
         if graphed is not None:
             logits = graphed.step(seq[:, pos])
         else:

@@ -174,6 +174,44 @@ def has_ext_decode_sample() -> bool:
     return _EXT_DECODE_SAMPLE is not None
 
 
+# the kernels that prefill the decode caches from one forward over the
+# prime: a fifth module (progen_amd._C_prefill, ops/hip/prefill_bindings.cpp)
+_EXT_PREFILL: Optional[Any] = None
+_EXT_PREFILL_ERR: Optional[str] = None
+_TRIED_PREFILL = False
+
+
+def _try_load_prefill() -> None:
+    global _EXT_PREFILL, _EXT_PREFILL_ERR, _TRIED_PREFILL
+    if _TRIED_PREFILL:
+        return
+    _TRIED_PREFILL = True
+    try:
+        _EXT_PREFILL = importlib.import_module("progen_amd._C_prefill")
+    except Exception as e:  # noqa: BLE001 - record and re-raise on GPU use
+        _EXT_PREFILL = None
+        _EXT_PREFILL_ERR = f"{type(e).__name__}: {e}"
+
+
+def ext_prefill() -> Any:
+    """Return the loaded prefill extension, raising loudly if unavailable —
+    a prefill on a GPU never falls back to torch ops."""
+    _try_load_prefill()
+    if _EXT_PREFILL is None:
+        raise RuntimeError(
+            "progen_amd prefill extension (progen_amd._C_prefill) is not "
+            f"available (import error: {_EXT_PREFILL_ERR}). Build it in-tree "
+            "with `python setup.py build_ext --inplace` "
+            "(PYTORCH_ROCM_ARCH=gfx950)."
+        )
+    return _EXT_PREFILL
+
+
+def has_ext_prefill() -> bool:
+    _try_load_prefill()
+    return _EXT_PREFILL is not None
+
+
 def use_hip(t, op: str = None) -> bool:
     """True when tensor t lives on a ROCm GPU (→ HIP kernels are mandatory).
 
@@ -183,7 +221,8 @@ def use_hip(t, op: str = None) -> bool:
       the per-kernel bisect lever for the graphed-replay investigation
       (profiles/r02_graphed_nan_investigation.md). Tags: ln, attn, glu,
       sgu, ce, adamw; the fused decode step's ops are dec_ln, dec_attn,
-      dec_sgu, dec_linear and dec_sample.
+      dec_sgu, dec_linear and dec_sample; the prefill's are prefill_kv
+      and prefill_gate.
     """
     if not t.is_cuda:
         return False

@@ -413,6 +413,92 @@ def decode_linear(x: torch.Tensor, w: torch.Tensor, bias, act: str = "none"
 
 
 # ---------------------------------------------------------------------------
+# prefill of the decode caches (ops/hip/prefill.hip)
+# ---------------------------------------------------------------------------
+# One full-sequence forward over the prime leaves in the caches what the
+# decode steps of its positions would have stored. ``P`` is a host int; only
+# cache rows [0, P) are written. Everything runs in the inputs' dtype.
+
+def prefill_rope_kv(
+    qkv: torch.Tensor,
+    rsin: torch.Tensor,
+    rcos: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    P: int,
+) -> torch.Tensor:
+    """Interleaved rotary on q, k and v of qkv (B, N, 3*H*dh) at positions
+    0..N-1; the rotated k and v of rows < P are stored head-major into
+    k_cache/v_cache (B, H, Nc, dh). Returns the rotated qkv."""
+    B, N, C = qkv.shape
+    _, H, Nc, dh = k_cache.shape
+    if not 1 <= P <= min(N, Nc):
+        raise ValueError(f"prefill_rope_kv: P must be in [1, {min(N, Nc)}], "
+                         f"got {P}")
+    x = qkv.reshape(B, N, 3 * H, dh)
+    s = rsin[:N].to(qkv.dtype).reshape(1, N, 1, dh)
+    c = rcos[:N].to(qkv.dtype).reshape(1, N, 1, dh)
+    rot = x * c + rotate_every_two(x) * s
+    k_cache[:, :, :P] = rot[:, :P, H:2 * H].transpose(1, 2)
+    v_cache[:, :, :P] = rot[:, :P, 2 * H:].transpose(1, 2)
+    return rot.reshape(B, N, C)
+
+
+def prefill_attention(
+    qkv: torch.Tensor,
+    rsin: torch.Tensor,
+    rcos: torch.Tensor,
+    heads: int,
+    window: int,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    P: int,
+) -> torch.Tensor:
+    """``local_attention`` over the whole (B, N, 3*H*dh) qkv, with the
+    rotated k/v rows < P left in the caches."""
+    N = qkv.shape[1]
+    prefill_rope_kv(qkv, rsin, rcos, k_cache, v_cache, P)
+    return local_attention(qkv, rsin[:N], rcos[:N], heads, window)
+
+
+def prefill_gate_ln(
+    x: torch.Tensor,
+    g: torch.Tensor,
+    hist: torch.Tensor,
+    P: int,
+    eps: float = 1e-5,
+) -> torch.Tensor:
+    """Scale-only LN of the gate half of x (B, N, 2*d2); rows < P are stored
+    into hist (B, Nc, d2). Returns the (B, N, d2) LN'd gate."""
+    N, Nc = x.shape[1], hist.shape[1]
+    if not 1 <= P <= min(N, Nc):
+        raise ValueError(f"prefill_gate_ln: P must be in [1, {min(N, Nc)}], "
+                         f"got {P}")
+    gate_ln = layernorm_nobias(x.chunk(2, dim=-1)[1], g, eps)
+    hist[:, :P] = gate_ln[:, :P]
+    return gate_ln
+
+
+def prefill_sgu(
+    x: torch.Tensor,
+    g: torch.Tensor,
+    w: torch.Tensor,
+    bias: torch.Tensor,
+    hist: torch.Tensor,
+    P: int,
+    eps: float = 1e-5,
+) -> torch.Tensor:
+    """``sgu_gate`` over the whole (B, N, 2*d2) activation, with the LN'd
+    gate rows < P left in ``hist``."""
+    n = x.shape[1]
+    gate_ln = prefill_gate_ln(x, g, hist, P, eps)
+    wl = w[:n, :n].tril().to(gate_ln.dtype)
+    gate = torch.einsum("bnd,mn->bmd", gate_ln, wl) + \
+        bias[:n].to(gate_ln.dtype)
+    return x.chunk(2, dim=-1)[0] * gate
+
+
+# ---------------------------------------------------------------------------
 # decode-step sampler (ops/hip/decode_sample.hip)
 # ---------------------------------------------------------------------------
 # The device sampler draws its uniforms from Philox4x32-10, a stateless

@@ -38,10 +38,15 @@ load_dotenv()  # reference: sample.py:1-2
               is_flag=True,
               help='with --cached: sample on the device, inside the step '
                    '(--seed then keys the device sampler\'s own stream)')
+@click.option('--prefill', default=False, is_flag=True,
+              help='with --cached: build the prime\'s cache with one forward '
+                   'over the prime instead of one decode step per token')
 def main(seed, checkpoint_path, prime, fast, cached, graph, fused,
-         fused_linear, device_sampling):
+         fused_linear, device_sampling, prefill):
     if fused_linear and not fused:
         raise click.UsageError('--fused-linear needs --fused')
+    if prefill and not cached:
+        raise click.UsageError('--prefill needs --cached')
     if device_sampling and not cached:
         raise click.UsageError('--device-sampling needs --cached')
     from progen_amd.tuning import enable_tuned_gemms
@@ -89,7 +94,8 @@ def main(seed, checkpoint_path, prime, fast, cached, graph, fused,
             else dict(generator=g)
         sampled = sample_cached(module, prime_tensor, seq_len, top_k=25,
                                 add_bos=True, graph=graph, fused=fused,
-                                fused_linear=fused_linear, **sampling)
+                                fused_linear=fused_linear, prefill=prefill,
+                                **sampling)
     elif fast:
         sampled = sample_fast(fwd, prime_tensor, seq_len, top_k=25,
                               add_bos=True, generator=g,

@@ -48,6 +48,7 @@ def create_app(module: ProGenBase, cfg: ProGenConfig, *,
                graph: bool = False, fused: bool = False,
                fused_linear: bool = False,
                device_sampling: bool = False,
+               prefill: bool = False,
                meta: Optional[dict] = None):
     """Build the FastAPI app around a ready (device-placed, eval) module."""
     if fused_linear and not fused:
@@ -67,6 +68,7 @@ def create_app(module: ProGenBase, cfg: ProGenConfig, *,
         "fused": bool(fused),
         "fused_linear": bool(fused_linear),
         "device_sampling": bool(device_sampling),
+        "prefill": bool(prefill),
         **(meta or {}),
     }
 
@@ -121,6 +123,7 @@ def create_app(module: ProGenBase, cfg: ProGenConfig, *,
                                       graph=info["graph"],
                                       fused=info["fused"],
                                       fused_linear=info["fused_linear"],
+                                      prefill=info["prefill"],
                                       **sampling)
         ms = (time.perf_counter() - t0) * 1e3
         seqs, toks_out = [], []
@@ -175,8 +178,11 @@ def load_module(checkpoint_path: str):
               help="sample on the device, inside the step (with --graph: "
                    "inside the captured graph); a request's seed then keys "
                    "the device sampler's own stream")
+@click.option("--prefill", default=False, is_flag=True,
+              help="build the cache of a request's common prime prefix with "
+                   "one forward instead of one decode step per token")
 def main(checkpoint_path, host, port, graph, fused, fused_linear,
-         device_sampling):
+         device_sampling, prefill):
     if fused_linear and not fused:
         raise click.UsageError("--fused-linear needs --fused")
     load_dotenv()
@@ -186,7 +192,8 @@ def main(checkpoint_path, host, port, graph, fused, fused_linear,
     module, cfg, meta = load_module(checkpoint_path)
     app = create_app(module, cfg, graph=graph, fused=fused,
                      fused_linear=fused_linear,
-                     device_sampling=device_sampling, meta=meta)
+                     device_sampling=device_sampling, prefill=prefill,
+                     meta=meta)
     uvicorn.run(app, host=host, port=port, log_level="info")
 
 

@@ -1,6 +1,6 @@
 """In-tree build of the progen_amd._C, progen_amd._C_decode,
-progen_amd._C_decode_linear and progen_amd._C_decode_sample HIP extensions
-(gfx950 only).
+progen_amd._C_decode_linear, progen_amd._C_decode_sample and
+progen_amd._C_prefill HIP extensions (gfx950 only).
 
     PYTORCH_ROCM_ARCH=gfx950 python setup.py build_ext --inplace
 
@@ -52,6 +52,13 @@ DECODE_SAMPLE_SOURCES = [
     "progen_amd/ops/hip/decode_sample.hip",
 ]
 
+# the kernels that fill the decode caches from one forward over the prime; a
+# fifth module for the same reason
+PREFILL_SOURCES = [
+    "progen_amd/ops/hip/prefill_bindings.cpp",
+    "progen_amd/ops/hip/prefill.hip",
+]
+
 COMPILE_ARGS = {
     "cxx": ["-O3", "-std=c++17"],
     "nvcc": ["-O3", "-std=c++17"],
@@ -78,6 +85,11 @@ setup(
         CUDAExtension(
             name="progen_amd._C_decode_sample",
             sources=DECODE_SAMPLE_SOURCES,
+            extra_compile_args=COMPILE_ARGS,
+        ),
+        CUDAExtension(
+            name="progen_amd._C_prefill",
+            sources=PREFILL_SOURCES,
             extra_compile_args=COMPILE_ARGS,
         ),
     ],

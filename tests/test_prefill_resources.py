@@ -1,0 +1,52 @@
+"""Build-time resource check of the prefill kernels (CPU; hipcc
+cross-compiles for gfx950 without a device), after
+tests/test_decode_sample_resources.py.
+
+Both are row kernels that hold a row's 16 B vectors in registers between
+their passes. A spill to scratch would be silent, so the compiler's own
+resource-usage remark is read back here and the table printed.
+"""
+
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SRC = os.path.join(HERE, "..", "progen_amd", "ops", "hip", "prefill.hip")
+
+
+def _hipcc():
+    return shutil.which("hipcc") or (
+        "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
+
+
+@pytest.mark.skipif(_hipcc() is None, reason="needs hipcc")
+def test_prefill_kernels_use_no_scratch(tmp_path):
+    r = subprocess.run(
+        [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17",
+         "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
+         "-c", SRC, "-o", str(tmp_path / "prefill.o")],
+        capture_output=True, text=True, check=True)
+    usage = {}
+    name = None
+    for line in r.stderr.splitlines():
+        m = re.search(r"remark:\s+Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            usage[name] = {}
+            continue
+        m = re.search(r"remark:\s+(SGPRs|VGPRs|AGPRs|"
+                      r"ScratchSize \[bytes/lane\]|"
+                      r"Occupancy \[waves/SIMD\]|"
+                      r"LDS Size \[bytes/block\]): (\d+)", line)
+        if m and name:
+            usage[name][m.group(1).split(" ")[0]] = int(m.group(2))
+    for kernel in ("prefill_rope_kv_kernel", "prefill_gate_ln_kernel"):
+        assert len([k for k in usage if kernel in k]) == 1, sorted(usage)
+    assert len(usage) == 2, sorted(usage)
+    for k, u in usage.items():
+        print(f"RESOURCE|{k}|{u}")
+        assert u["ScratchSize"] == 0, (k, u)

@@ -13,11 +13,19 @@ downloads the pad counts every --check-every steps); greedy, or top-k
 gumbel-max with --top-k K in either arm.
 Serving metric: ms/token (batch 1) and tokens/s aggregate.
 
+With --prime-len N it measures whole requests instead, through the public
+samplers (``sample_cached`` at batch 1, ``sample_cached_batch`` above): the
+time from the call to the first sampled token after an N-token prime, and
+the rate of tokens 2..--tokens; --prefill builds the prime's cache with one
+forward (``decode.prefill``) instead of one step per prime token.
+
 Usage (GPU box):  python tools/bench_decode.py [--tokens 128] [--graph] [--fused [--fused-linear]] [--batch 8] [--device-sampling] [--top-k 25]
+                  python tools/bench_decode.py --prime-len 512 [--prefill] --graph --fused --fused-linear [--batch 8]
 """
 
 import argparse
 import os
+import statistics
 import sys
 import time
 
@@ -28,7 +36,8 @@ import torch
 from progen_amd import ProGenBase
 from progen_amd.config import ProGenConfig
 from progen_amd.decode import (DecodeCache, DeviceSampler, GraphedDecodeStep,
-                               forward_step, forward_step_fused)
+                               forward_step, forward_step_fused,
+                               sample_cached, sample_cached_batch)
 from progen_amd.ops import reference as R
 
 
@@ -53,7 +62,21 @@ def parse_args(argv=None):
                     help="with --device-sampling: steps between pad-count "
                          "downloads")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--prime-len", type=int, default=0,
+                    help="measure whole requests with a prime of this many "
+                         "tokens: time to the first sampled token, then the "
+                         "rate of tokens 2..--tokens (0: the step benchmark)")
+    ap.add_argument("--prefill", action="store_true",
+                    help="with --prime-len: one forward over the prime "
+                         "instead of one decode step per prime token")
+    ap.add_argument("--repeats", type=int, default=5,
+                    help="with --prime-len: timed requests of each kind; "
+                         "the median is reported")
     args = ap.parse_args(argv)
+    if args.prefill and not args.prime_len:
+        ap.error("--prefill needs --prime-len")
+    if args.prime_len < 0 or args.repeats < 1:
+        ap.error("--prime-len must be >= 0 and --repeats >= 1")
     if args.fused_linear and not args.fused:
         ap.error("--fused-linear needs --fused")
     if args.top_k < 0 or args.check_every < 1:
@@ -212,9 +235,68 @@ def _run_device_sampling(m, args, cache, tok):
     return mode, t0
 
 
+def run_prime(m, args):
+    """Whole requests with an ``args.prime_len``-token prime, as the samplers
+    serve them: returns (median ms to the first sampled token, median ms per
+    token for tokens 2..--tokens). A request for one token ends when that
+    token is on the host; one for --tokens tokens adds the decode steps, and
+    the difference of the two is their time. With --graph both include the
+    capture of the step."""
+    B, N = args.batch, args.prime_len
+    if N + args.tokens > m.cfg.seq_len or args.tokens < 2:
+        raise SystemExit("--prime-len + --tokens must stay within seq_len "
+                         "and --tokens above 1")
+    with torch.no_grad():
+        # a request that samples its second pad ends early: rule token 0 out
+        m.to_logits.bias[0] = -1e4
+    g = torch.Generator().manual_seed(args.seed)
+    primes = torch.randint(1, 256, (B, N), generator=g)
+    kw = dict(graph=args.graph, fused=args.fused,
+              fused_linear=args.fused_linear, prefill=args.prefill,
+              top_k=args.top_k or None)
+    if args.device_sampling:
+        kw.update(device_sampling=True, check_every=args.check_every,
+                  seed=args.seed if args.top_k else None)
+
+    def request(length):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if B == 1:
+            out = sample_cached(m, primes[0], length, **kw)
+        else:
+            out = sample_cached_batch(m, list(primes), length, **kw)
+        torch.cuda.synchronize()
+        assert bool((out[..., :length] != 0).all()), "a request ended early"
+        return 1e3 * (time.perf_counter() - t0)
+
+    for _ in range(max(1, min(args.warmup, 2))):    # every shape, both kinds
+        request(N + 1)
+        request(N + args.tokens)
+    first, rest = [], []
+    for _ in range(args.repeats):
+        t1 = request(N + 1)
+        tn = request(N + args.tokens)
+        first.append(t1)
+        rest.append((tn - t1) / (args.tokens - 1))
+    ttft, per_tok = statistics.median(first), statistics.median(rest)
+    mode = ("graphed" if args.graph else "eager") + \
+        ("+fused" if args.fused else "") + \
+        ("+linear" if args.fused_linear else "") + \
+        ("+devsample" if args.device_sampling else "") + \
+        ("+prefill" if args.prefill else "")
+    print(f"request[{mode}, batch {B}, prime {N}]: first token after "
+          f"{ttft:.1f} ms (min {min(first):.1f}, max {max(first):.1f}), "
+          f"tokens 2..{args.tokens} at {per_tok:.2f} ms/token "
+          f"(median of {args.repeats}; ProGen-1.2B flagship config, bf16)")
+    return ttft, per_tok
+
+
 def main():
     args = parse_args()
-    run(flagship(), args)
+    if args.prime_len:
+        run_prime(flagship(), args)
+    else:
+        run(flagship(), args)
 
 
 if __name__ == "__main__":
