@@ -287,7 +287,44 @@ def forward_step_fused(model: ProGenBase, token: torch.Tensor,
     the bias and the GLU/GELU of ``proj_in`` folded in: 7 launches per GLU
     layer and 9 per SGU layer, and no bias copy. On the CPU it computes
     the same ops as the default, bit for bit."""
+    return _fused_step(model, token, cache, pos_dev, fused_linear,
+                       slots=False)
+
+
+@torch.no_grad()
+def forward_step_slots(model: ProGenBase, token: torch.Tensor,
+                       cache: DecodeCache, pos: torch.Tensor,
+                       fused_linear: bool = False) -> torch.Tensor:
+    """``forward_step_fused`` with one position per batch row: ``pos`` is a
+    (B,) int64 device tensor and row b of the same ``DecodeCache`` advances
+    at pos[b]. A row with pos[b] < 0 is idle: none of its cache rows, shift
+    halos or histories change, and it flows through the projections as
+    zeros. A row at position 0 starts on a clean slate whatever its cache
+    row still holds from an earlier request: its token shift reads zeros and
+    the attention band and the SGU prefix only ever reach rows the request
+    wrote itself. Positions are NOT advanced here — ``OF.decode_sample_slots``
+    does that, and retires finished rows. Same ops and launch counts as
+    ``forward_step_fused``, on the slot kernels (ops/hip/decode_slots.hip on
+    a GPU, ops/reference.py on CPU)."""
+    return _fused_step(model, token, cache, pos, fused_linear, slots=True)
+
+
+def _fused_step(model: ProGenBase, token: torch.Tensor, cache: DecodeCache,
+                pos_dev: torch.Tensor, fused_linear: bool,
+                slots: bool) -> torch.Tensor:
+    """The layer loop of ``forward_step_fused`` (``pos_dev`` 0-dim) and
+    ``forward_step_slots`` (``pos_dev`` (B,)): the two differ only in which
+    set of ops reads the position."""
     cfg = model.cfg
+    if slots:
+        def ln_shift(h, r, weight, prev, shift):
+            return OF.decode_ln_shift_slots(h, r, weight, prev, pos_dev,
+                                            shift=shift)
+        attention, sgu_row = OF.decode_attention_slots, OF.decode_sgu_slots
+    else:
+        def ln_shift(h, r, weight, prev, shift):
+            return OF.decode_ln_shift(h, r, weight, prev, shift=shift)
+        attention, sgu_row = OF.decode_attention, OF.decode_sgu
     if fused_linear:
         def linear(x, lin, act="none"):
             return OF.decode_linear(x, lin.weight, lin.bias, act)
@@ -305,24 +342,23 @@ def forward_step_fused(model: ProGenBase, token: torch.Tensor,
     h = model.embed(token.long().reshape(-1))           # (B, dim), updated in place
     r = None
     for li, (attn, ff) in enumerate(model.layers):
-        y = OF.decode_ln_shift(h, r, attn.norm_weight, cache.attn_prev[li],
-                               shift=attn.shift_tokens)
+        y = ln_shift(h, r, attn.norm_weight, cache.attn_prev[li],
+                     attn.shift_tokens)
         qkv = linear(y, attn.to_qkv)
-        out = OF.decode_attention(qkv, sin, cos, pos_dev, cache.k[li],
-                                  cache.v[li], attn.window_size)
+        out = attention(qkv, sin, cos, pos_dev, cache.k[li], cache.v[li],
+                        attn.window_size)
         a = linear(out, attn.to_out)
 
-        y = OF.decode_ln_shift(h, a, ff.norm_weight, cache.ff_prev[li],
-                               shift=ff.shift_tokens)
+        y = ln_shift(h, a, ff.norm_weight, cache.ff_prev[li],
+                     ff.shift_tokens)
         t = linear(y, ff.proj_in, "glu" if ff.glu else "gelu")
         if ff.sgu is not None:
             sgu = ff.sgu
-            t = OF.decode_sgu(t, sgu.norm_weight, cache.gate_hist[li],
-                              sgu.spatial_weights, sgu.spatial_biases,
-                              pos_dev)
+            t = sgu_row(t, sgu.norm_weight, cache.gate_hist[li],
+                        sgu.spatial_weights, sgu.spatial_biases, pos_dev)
             t = linear(t, sgu.proj_out)
         r = linear(t, ff.proj_out)
-    y = OF.decode_ln_shift(h, r, model.final_norm_weight, None, shift=False)
+    y = ln_shift(h, r, model.final_norm_weight, None, False)
     return linear(y, model.to_logits)
 
 

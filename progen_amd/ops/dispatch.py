@@ -212,6 +212,46 @@ def has_ext_prefill() -> bool:
     return _EXT_PREFILL is not None
 
 
+# the decode kernels with one position per batch row: a sixth module
+# (progen_amd._C_decode_slots, ops/hip/decode_slots_bindings.cpp)
+_EXT_DECODE_SLOTS: Optional[Any] = None
+_EXT_DECODE_SLOTS_ERR: Optional[str] = None
+_TRIED_DECODE_SLOTS = False
+
+
+def _try_load_decode_slots() -> None:
+    global _EXT_DECODE_SLOTS, _EXT_DECODE_SLOTS_ERR, _TRIED_DECODE_SLOTS
+    if _TRIED_DECODE_SLOTS:
+        return
+    _TRIED_DECODE_SLOTS = True
+    try:
+        _EXT_DECODE_SLOTS = importlib.import_module(
+            "progen_amd._C_decode_slots")
+    except Exception as e:  # noqa: BLE001 - record and re-raise on GPU use
+        _EXT_DECODE_SLOTS = None
+        _EXT_DECODE_SLOTS_ERR = f"{type(e).__name__}: {e}"
+
+
+def ext_decode_slots() -> Any:
+    """Return the loaded slot-kernel extension, raising loudly if
+    unavailable — the slot step never falls back to torch ops."""
+    _try_load_decode_slots()
+    if _EXT_DECODE_SLOTS is None:
+        raise RuntimeError(
+            "progen_amd decode-slots extension "
+            "(progen_amd._C_decode_slots) is not available (import error: "
+            f"{_EXT_DECODE_SLOTS_ERR}). Build it in-tree with "
+            "`python setup.py build_ext --inplace` "
+            "(PYTORCH_ROCM_ARCH=gfx950)."
+        )
+    return _EXT_DECODE_SLOTS
+
+
+def has_ext_decode_slots() -> bool:
+    _try_load_decode_slots()
+    return _EXT_DECODE_SLOTS is not None
+
+
 def use_hip(t, op: str = None) -> bool:
     """True when tensor t lives on a ROCm GPU (→ HIP kernels are mandatory).
 
@@ -221,8 +261,8 @@ def use_hip(t, op: str = None) -> bool:
       the per-kernel bisect lever for the graphed-replay investigation
       (profiles/r02_graphed_nan_investigation.md). Tags: ln, attn, glu,
       sgu, ce, adamw; the fused decode step's ops are dec_ln, dec_attn,
-      dec_sgu, dec_linear and dec_sample; the prefill's are prefill_kv
-      and prefill_gate.
+      dec_sgu, dec_linear and dec_sample (the slot step's ops answer to
+      the same four); the prefill's are prefill_kv and prefill_gate.
     """
     if not t.is_cuda:
         return False

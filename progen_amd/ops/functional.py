@@ -473,3 +473,71 @@ def decode_sample(logits: torch.Tensor, pos: torch.Tensor, seed: torch.Tensor,
         return
     reference.decode_sample(logits, pos, seed, seq, lens, pads, token,
                             top_k, greedy, u_out)
+
+
+# ---------------------------------------------------------------------------
+# slot decode-step ops (inference only; progen_amd._C_decode_slots)
+# ---------------------------------------------------------------------------
+# The four ops above with one position per batch row: ``pos`` is a (B,)
+# int64 device tensor and pos[b] < 0 marks an idle row, which changes
+# nothing and gets a zero output row — see decode.forward_step_slots and
+# progen_amd/engine.py. They answer to the routing tags of their twins.
+
+def decode_ln_shift_slots(h: torch.Tensor, res, weight: torch.Tensor, prev,
+                          pos: torch.Tensor, shift: bool = True,
+                          eps: float = 1e-5) -> torch.Tensor:
+    """``decode_ln_shift`` per row; a row at position 0 shifts in zeros
+    instead of ``prev`` (reference.decode_ln_shift_slots)."""
+    if dispatch.use_hip(h, "dec_ln"):
+        return dispatch.ext_decode_slots().dec_ln_shift_slots(
+            h, res, weight, prev, pos, bool(shift), float(eps))
+    return reference.decode_ln_shift_slots(h, res, weight, prev, pos, shift,
+                                           eps)
+
+
+def decode_attention_slots(qkv: torch.Tensor, sin: torch.Tensor,
+                           cos: torch.Tensor, pos: torch.Tensor,
+                           k_cache: torch.Tensor, v_cache: torch.Tensor,
+                           window_size: int) -> torch.Tensor:
+    """``decode_attention`` with row b at position pos[b]
+    (reference.decode_attention_slots)."""
+    if dispatch.use_hip(qkv, "dec_attn"):
+        return dispatch.ext_decode_slots().dec_attn_slots(
+            qkv, sin, cos, pos, k_cache, v_cache, int(window_size))
+    return reference.decode_attention_slots(qkv, sin, cos, pos, k_cache,
+                                            v_cache, window_size)
+
+
+def decode_sgu_slots(h: torch.Tensor, norm_weight: torch.Tensor,
+                     hist: torch.Tensor, spatial_weights: torch.Tensor,
+                     spatial_biases: torch.Tensor, pos: torch.Tensor,
+                     eps: float = 1e-5) -> torch.Tensor:
+    """``decode_sgu`` with row b at position pos[b]
+    (reference.decode_sgu_slots)."""
+    if dispatch.use_hip(h, "dec_sgu"):
+        return dispatch.ext_decode_slots().dec_sgu_slots(
+            h, norm_weight, hist, spatial_weights, spatial_biases, pos,
+            float(eps))
+    return reference.decode_sgu_slots(h, norm_weight, hist, spatial_weights,
+                                      spatial_biases, pos, eps)
+
+
+# columns of the slot sampler's per-row controls
+SLOT_CTL = ("len", "limit", "top_k", "seed", "stream")
+
+
+def decode_sample_slots(logits: torch.Tensor, pos: torch.Tensor,
+                        token: torch.Tensor, seq: torch.Tensor,
+                        pads: torch.Tensor, ctl: torch.Tensor,
+                        u_out=None) -> None:
+    """Sample position pos[b] + 1 of every live row under its own controls
+    ``ctl[b] = [len, limit, top_k, seed, stream]`` into ``seq``, ``pads`` and
+    ``token``, and advance or retire the row in ``pos``, all in place
+    (reference.decode_sample_slots). On a GPU this is the HIP kernel, which a
+    graph can capture; a vocabulary it does not serve is an error there,
+    never a fall-back."""
+    if dispatch.use_hip(logits, "dec_sample"):
+        dispatch.ext_decode_slots().dec_sample_slots(
+            logits, pos, token, seq, pads, ctl, u_out)
+        return
+    reference.decode_sample_slots(logits, pos, token, seq, pads, ctl, u_out)

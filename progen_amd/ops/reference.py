@@ -611,3 +611,140 @@ def decode_sample(
     seq[:, w] = col
     pads.add_((col == 0).long())
     token.copy_(col)
+
+
+# ---------------------------------------------------------------------------
+# slot twins of the decode-step ops (progen_amd._C_decode_slots)
+# ---------------------------------------------------------------------------
+# One position per batch row: ``pos`` is (B,) int64 and pos[b] < 0 marks an
+# idle row, which changes nothing and gets a zero output row. Each twin runs
+# the scalar reference above on the row views b:b+1, so a row computes what
+# it would compute alone at its position. The positions are read on the
+# host: like ``decode_sample`` these cannot be captured in a graph.
+
+def _slot_positions(pos: torch.Tensor, B: int, n: int):
+    """(row, 0-dim position tensor) of every live row of a (B,) ``pos``;
+    positions outside [0, n) are idle, as in the kernels."""
+    assert pos.shape == (B,), f"pos must be ({B},), got {tuple(pos.shape)}"
+    return [(b, pos[b]) for b, p in enumerate(pos.tolist()) if 0 <= p < n]
+
+
+def decode_ln_shift_slots(
+    h: torch.Tensor,
+    res: Optional[torch.Tensor],
+    g: torch.Tensor,
+    prev: Optional[torch.Tensor],
+    pos: torch.Tensor,
+    shift: bool,
+    eps: float = 1e-5,
+) -> torch.Tensor:
+    """``decode_ln_shift`` per row. A row at position 0 starts a request in a
+    slot whose ``prev`` row belongs to the one before it: its shifted half is
+    zeros. An idle row keeps its ``h`` and ``prev``."""
+    y = torch.zeros_like(h)
+    for b, p in enumerate(pos.tolist()):
+        if p < 0:
+            continue
+        pb = None if prev is None else prev[b:b + 1]
+        # at position 0 the shifted half is read from a zero stand-in; what
+        # the scalar reference leaves in it (the LN row) goes to the real row
+        rd = torch.zeros_like(pb) if p == 0 and pb is not None else pb
+        y[b:b + 1] = decode_ln_shift(
+            h[b:b + 1], None if res is None else res[b:b + 1], g, rd, shift,
+            eps)
+        if rd is not pb:
+            pb.copy_(rd)
+    return y
+
+
+def decode_attention_slots(
+    qkv: torch.Tensor,
+    rsin: torch.Tensor,
+    rcos: torch.Tensor,
+    pos: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    window: int,
+) -> torch.Tensor:
+    """``decode_attention`` per row, row b at position pos[b]."""
+    B, H, N, dh = k_cache.shape
+    out = qkv.new_zeros(B, H * dh)
+    for b, p in _slot_positions(pos, B, N):
+        out[b:b + 1] = decode_attention(
+            qkv[b:b + 1], rsin, rcos, p, k_cache[b:b + 1], v_cache[b:b + 1],
+            window)
+    return out
+
+
+def decode_sgu_slots(
+    h: torch.Tensor,
+    g: torch.Tensor,
+    hist: torch.Tensor,
+    w: torch.Tensor,
+    bias: torch.Tensor,
+    pos: torch.Tensor,
+    eps: float = 1e-5,
+) -> torch.Tensor:
+    """``decode_sgu`` per row, row b at position pos[b]."""
+    B, N, d2 = hist.shape
+    out = h.new_zeros(B, d2)
+    for b, p in _slot_positions(pos, B, N):
+        out[b:b + 1] = decode_sgu(h[b:b + 1], g, hist[b:b + 1], w, bias, p,
+                                  eps)
+    return out
+
+
+def decode_sample_slots(
+    logits: torch.Tensor,
+    pos: torch.Tensor,
+    token: torch.Tensor,
+    seq: torch.Tensor,
+    pads: torch.Tensor,
+    ctl: torch.Tensor,
+    u_out: Optional[torch.Tensor] = None,
+) -> None:
+    """``decode_sample`` with a position and a control row per batch row, in
+    place; the sampler also owns the position advance and the retirement.
+
+    logits (B, V); pos, token, pads (B,) and seq (B, L) int64; ctl (B, 5)
+    int64 with columns [len, limit, top_k, seed, stream]. For row b with
+    p = pos[b] >= 0 and w = p + 1: if w >= limit the row retires (pos[b] = -1)
+    and nothing else changes. Else its token is the first argmax of
+    ``decode_sample_scores``: greedy when seed < 0, else with ``top_k`` (0:
+    the whole row) and row ``stream`` of the uniforms
+    ``decode_sample_uniform(seed, w, stream + 1, V)``, i.e. the Philox counter
+    (j / 4, w, stream, 0). It is written to seq[b, w] unless the prime covers
+    w (w < len); then pads[b] += (seq[b, w] == 0), token[b] = seq[b, w] and
+    pos[b] = -1 if pads[b] >= 2 or w + 1 >= limit, else w. ``u_out`` (B, V)
+    fp32 receives the uniforms of the rows that drew any."""
+    if logits.is_cuda and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(
+            "decode_sample_slots: the reference sampler reads the positions "
+            "on the host and cannot be captured in a graph; capture needs the "
+            "HIP kernel (do not list dec_sample in PROGEN_EAGER_OPS)")
+    B, V = logits.shape
+    L = seq.shape[1]
+    rows = logits.detach().cpu()
+    for b, p in enumerate(pos.tolist()):
+        if p < 0:
+            continue
+        w = p + 1
+        n, limit, top_k, seed, stream = ctl[b].tolist()
+        if w >= limit or w >= L:
+            pos[b] = -1
+            continue
+        greedy = seed < 0
+        u = None
+        if not greedy:
+            u = decode_sample_uniform(seed, w, stream + 1, V)[stream:stream + 1]
+            if u_out is not None:
+                u_out[b:b + 1].copy_(u)
+        scores = decode_sample_scores(rows[b:b + 1], u, top_k, greedy)
+        tok = int(scores.argmax(dim=-1))  # first maximal index
+        if w >= n:
+            seq[b, w] = tok
+        else:
+            tok = int(seq[b, w])
+        pads[b] += int(tok == 0)
+        token[b] = tok
+        pos[b] = -1 if (int(pads[b]) >= 2 or w + 1 >= limit) else w

@@ -28,8 +28,16 @@ profiles/r02_fp8_and_decode.md). With --graph the per-token step is
 captured per request (the decoder manages its own capture); the capture
 cost amortizes over the generated length — persistent cross-request
 capture keyed on batch shape is the next step if request shapes repeat.
+
+With --slots N (needs --fused and --device-sampling) requests do not take
+the lock: they go through one ``progen_amd.engine.SlotEngine``, a persistent
+decode batch of N rows in which every row serves its own request at its own
+position. Concurrent requests then share each decode step, a finished row
+frees its slot at once, and with --graph the step is captured once for the
+life of the server.
 """
 
+import contextlib
 import threading
 import time
 from typing import List, Optional
@@ -49,14 +57,25 @@ def create_app(module: ProGenBase, cfg: ProGenConfig, *,
                fused_linear: bool = False,
                device_sampling: bool = False,
                prefill: bool = False,
+               slots: int = 0,
                meta: Optional[dict] = None):
-    """Build the FastAPI app around a ready (device-placed, eval) module."""
+    """Build the FastAPI app around a ready (device-placed, eval) module.
+    ``slots`` > 0 serves /generate from one started ``SlotEngine`` of that
+    many rows; the thread it starts then owns the module's device calls."""
     if fused_linear and not fused:
         raise ValueError("fused_linear=True needs fused=True")
+    _check_slots(slots, fused, device_sampling, prefill, ValueError)
     from fastapi import FastAPI, HTTPException
     from pydantic import BaseModel
 
-    app = FastAPI(title="progen-mi355x", docs_url=None, redoc_url=None)
+    @contextlib.asynccontextmanager
+    async def lifespan(_app):
+        yield
+        if engine is not None:
+            engine.close()  # finishes what is decoding, stops the worker
+
+    app = FastAPI(title="progen-mi355x", docs_url=None, redoc_url=None,
+                  lifespan=lifespan)
     lock = threading.Lock()
     device = next(module.parameters()).device
     info = {
@@ -69,8 +88,14 @@ def create_app(module: ProGenBase, cfg: ProGenConfig, *,
         "fused_linear": bool(fused_linear),
         "device_sampling": bool(device_sampling),
         "prefill": bool(prefill),
+        "slots": int(slots),
         **(meta or {}),
     }
+    engine = None
+    if slots:
+        from progen_amd.engine import SlotEngine
+        engine = SlotEngine(module, slots, graph=info["graph"],
+                            fused_linear=fused_linear).start()
 
     class GenerateRequest(BaseModel):
         primes: Optional[List[str]] = None
@@ -118,13 +143,17 @@ def create_app(module: ProGenBase, cfg: ProGenConfig, *,
                 generator=torch.Generator().manual_seed(req.seed)
                 if req.seed is not None else None)
         t0 = time.perf_counter()
-        with lock, torch.no_grad():
-            out = sample_cached_batch(module, rows, length, top_k=top_k,
-                                      graph=info["graph"],
-                                      fused=info["fused"],
-                                      fused_linear=info["fused_linear"],
-                                      prefill=info["prefill"],
-                                      **sampling)
+        if engine is not None:
+            # no lock: the engine batches concurrent requests itself
+            out = engine.generate(rows, length, top_k=top_k, seed=req.seed)
+        else:
+            with lock, torch.no_grad():
+                out = sample_cached_batch(module, rows, length, top_k=top_k,
+                                          graph=info["graph"],
+                                          fused=info["fused"],
+                                          fused_linear=info["fused_linear"],
+                                          prefill=info["prefill"],
+                                          **sampling)
         ms = (time.perf_counter() - t0) * 1e3
         seqs, toks_out = [], []
         for row, prime_row in zip(out, rows):
@@ -134,6 +163,25 @@ def create_app(module: ProGenBase, cfg: ProGenConfig, *,
         return {"sequences": seqs, "tokens": toks_out, "ms": ms}
 
     return app
+
+
+def _check_slots(slots, fused, device_sampling, prefill, error,
+                 opt=str) -> None:
+    """``slots`` runs the fused step with the device sampler and has no
+    prefill at admission; anything else is a usage error. ``opt`` spells an
+    option's name for the message."""
+    if slots < 0:
+        raise error(f"{opt('slots')} must be >= 0")
+    if not slots:
+        return
+    if not (fused and device_sampling):
+        raise error(f"{opt('slots')} needs {opt('fused')} and "
+                    f"{opt('device_sampling')}: the slot engine runs the "
+                    "fused decode step with the device sampler")
+    if prefill:
+        raise error(f"{opt('slots')} cannot be combined with "
+                    f"{opt('prefill')}: the slot engine feeds a prime "
+                    "through the shared step")
 
 
 def load_module(checkpoint_path: str):
@@ -181,10 +229,17 @@ def load_module(checkpoint_path: str):
 @click.option("--prefill", default=False, is_flag=True,
               help="build the cache of a request's common prime prefix with "
                    "one forward instead of one decode step per token")
+@click.option("--slots", default=0,
+              help="serve concurrent requests from one persistent decode "
+                   "batch of this many rows, each at its own position "
+                   "(needs --fused and --device-sampling; 0 = one request "
+                   "at a time)")
 def main(checkpoint_path, host, port, graph, fused, fused_linear,
-         device_sampling, prefill):
+         device_sampling, prefill, slots):
     if fused_linear and not fused:
         raise click.UsageError("--fused-linear needs --fused")
+    _check_slots(slots, fused, device_sampling, prefill, click.UsageError,
+                 opt=lambda name: "--" + name.replace("_", "-"))
     load_dotenv()
     from progen_amd.tuning import enable_tuned_gemms
     enable_tuned_gemms()
@@ -193,7 +248,7 @@ def main(checkpoint_path, host, port, graph, fused, fused_linear,
     app = create_app(module, cfg, graph=graph, fused=fused,
                      fused_linear=fused_linear,
                      device_sampling=device_sampling, prefill=prefill,
-                     meta=meta)
+                     slots=slots, meta=meta)
     uvicorn.run(app, host=host, port=port, log_level="info")
 
 

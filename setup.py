@@ -1,6 +1,7 @@
 """In-tree build of the progen_amd._C, progen_amd._C_decode,
-progen_amd._C_decode_linear, progen_amd._C_decode_sample and
-progen_amd._C_prefill HIP extensions (gfx950 only).
+progen_amd._C_decode_linear, progen_amd._C_decode_sample,
+progen_amd._C_prefill and progen_amd._C_decode_slots HIP extensions (gfx950
+only).
 
     PYTORCH_ROCM_ARCH=gfx950 python setup.py build_ext --inplace
 
@@ -8,6 +9,7 @@ The built .so files land next to the package (progen_amd/_C*.so) so the
 repo snapshot carries them to the GPU box.
 """
 
+import glob
 import os
 
 from setuptools import setup
@@ -59,6 +61,32 @@ PREFILL_SOURCES = [
     "progen_amd/ops/hip/prefill.hip",
 ]
 
+# the decode kernels with one position per batch row (progen_amd/engine.py);
+# a sixth module for the same reason. The kernel bodies are the
+# decode_*_body.h headers shared with the four scalar kernels above
+DECODE_SLOTS_SOURCES = [
+    "progen_amd/ops/hip/decode_slots_bindings.cpp",
+    "progen_amd/ops/hip/decode_slots.hip",
+]
+
+# Headers the .hip sources include (the decode kernel bodies among them are
+# shared by five of the files above). The ninja rule generated for .hip
+# sources records no header dependencies, so BuildHip drops every .hip object
+# older than the newest header before ninja decides what is up to date.
+HIP_HEADERS = sorted(h for h in glob.glob("progen_amd/ops/hip/*.h")
+                     if not h.endswith("_hip.h"))
+
+
+class BuildHip(BuildExtension):
+    def build_extension(self, ext):
+        newest = max(os.path.getmtime(h) for h in HIP_HEADERS)
+        pattern = os.path.join(self.build_temp, "**", "ops", "hip", "*_hip.o")
+        for obj in glob.glob(pattern, recursive=True):
+            if os.path.getmtime(obj) < newest:
+                os.remove(obj)
+        super().build_extension(ext)
+
+
 COMPILE_ARGS = {
     "cxx": ["-O3", "-std=c++17"],
     "nvcc": ["-O3", "-std=c++17"],
@@ -71,27 +99,38 @@ setup(
             name="progen_amd._C",
             sources=HIP_SOURCES,
             extra_compile_args=COMPILE_ARGS,
+            depends=HIP_HEADERS,
         ),
         CUDAExtension(
             name="progen_amd._C_decode",
             sources=DECODE_SOURCES,
             extra_compile_args=COMPILE_ARGS,
+            depends=HIP_HEADERS,
         ),
         CUDAExtension(
             name="progen_amd._C_decode_linear",
             sources=DECODE_LINEAR_SOURCES,
             extra_compile_args=COMPILE_ARGS,
+            depends=HIP_HEADERS,
         ),
         CUDAExtension(
             name="progen_amd._C_decode_sample",
             sources=DECODE_SAMPLE_SOURCES,
             extra_compile_args=COMPILE_ARGS,
+            depends=HIP_HEADERS,
         ),
         CUDAExtension(
             name="progen_amd._C_prefill",
             sources=PREFILL_SOURCES,
             extra_compile_args=COMPILE_ARGS,
+            depends=HIP_HEADERS,
+        ),
+        CUDAExtension(
+            name="progen_amd._C_decode_slots",
+            sources=DECODE_SLOTS_SOURCES,
+            extra_compile_args=COMPILE_ARGS,
+            depends=HIP_HEADERS,
         ),
     ],
-    cmdclass={"build_ext": BuildExtension.with_options(use_ninja=True)},
+    cmdclass={"build_ext": BuildHip.with_options(use_ninja=True)},
 )

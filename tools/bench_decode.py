@@ -19,8 +19,20 @@ time from the call to the first sampled token after an N-token prime, and
 the rate of tokens 2..--tokens; --prefill builds the prime's cache with one
 forward (``decode.prefill``) instead of one step per prime token.
 
+With --slots N it measures the slot engine (``progen_amd.engine``), which
+always runs graph-or-eager + fused + device sampling. Alone, --slots N
+compares one step of the engine's N-row batch with the scalar-position step
+(``GraphedDecodeStep`` with its sampler) at the same batch and positions,
+alternating the two --repeats times. With --requests M it serves M
+single-prime requests of seeded ragged lengths, all waiting at time 0:
+through the engine with N slots, or with --slots 0 one
+``sample_cached_batch`` per request in sequence, as serve.py runs them under
+its lock; it reports the wall time, generated tokens/s, the request latency
+percentiles and the engine's mean slot occupancy.
+
 Usage (GPU box):  python tools/bench_decode.py [--tokens 128] [--graph] [--fused [--fused-linear]] [--batch 8] [--device-sampling] [--top-k 25]
                   python tools/bench_decode.py --prime-len 512 [--prefill] --graph --fused --fused-linear [--batch 8]
+                  python tools/bench_decode.py --slots 16 --graph --fused --fused-linear --device-sampling --top-k 25 [--requests 64]
 """
 
 import argparse
@@ -38,6 +50,7 @@ from progen_amd.config import ProGenConfig
 from progen_amd.decode import (DecodeCache, DeviceSampler, GraphedDecodeStep,
                                forward_step, forward_step_fused,
                                sample_cached, sample_cached_batch)
+from progen_amd.engine import SlotEngine
 from progen_amd.ops import reference as R
 
 
@@ -72,7 +85,23 @@ def parse_args(argv=None):
     ap.add_argument("--repeats", type=int, default=5,
                     help="with --prime-len: timed requests of each kind; "
                          "the median is reported")
+    ap.add_argument("--slots", type=int, default=None,
+                    help="measure the slot engine with this many slots: its "
+                         "step against the scalar step, or with --requests "
+                         "a workload (0: the workload one request at a time)")
+    ap.add_argument("--requests", type=int, default=0,
+                    help="with --slots: serve this many single-prime requests "
+                         "of seeded prime lengths 4..64 and lengths 64..512")
     args = ap.parse_args(argv)
+    if args.slots is not None:
+        if not (args.fused and args.device_sampling) or args.prefill \
+                or args.prime_len:
+            ap.error("--slots needs --fused and --device-sampling, and "
+                     "takes neither --prefill nor --prime-len")
+        if args.slots < 0 or (args.slots == 0 and not args.requests):
+            ap.error("--slots must be >= 1, or 0 with --requests")
+    elif args.requests:
+        ap.error("--requests needs --slots")
     if args.prefill and not args.prime_len:
         ap.error("--prefill needs --prime-len")
     if args.prime_len < 0 or args.repeats < 1:
@@ -291,9 +320,186 @@ def run_prime(m, args):
     return ttft, per_tok
 
 
+def _spread(xs):
+    return (f"median {statistics.median(xs):.3f}, min {min(xs):.3f}, "
+            f"max {max(xs):.3f}")
+
+
+def run_slot_step(m, args):
+    """The slot step against the scalar-position step at batch --slots, all
+    rows active at equal positions, the two alternating --repeats times on
+    the same model; returns (scalar, slot) median ms per step. A timed block
+    is --tokens steps with a download every --check-every steps in both arms:
+    the scalar loop's pad counts, the engine's positions."""
+    B, T = args.slots, args.tokens
+    if 3 + args.warmup + T * args.repeats >= m.cfg.seq_len:
+        raise SystemExit("--warmup + --tokens * --repeats must stay below "
+                         "seq_len - 3")
+    with torch.no_grad():
+        m.to_logits.bias[0] = -1e4   # no row may finish early
+    g = torch.Generator().manual_seed(args.seed)
+    primes = torch.randint(1, 256, (B, 3), generator=g)
+    seed = args.seed if args.top_k else None
+
+    # scalar arm: as sample_cached_batch builds it, stepped from position 0
+    # through the prime like the engine's rows
+    seq = torch.zeros(B, m.cfg.seq_len, dtype=torch.long)
+    seq[:, :3] = primes
+    cache = DecodeCache(m, batch=B)
+    sampler = DeviceSampler(seq, [3] * B, args.top_k or None, seed, "cuda")
+    if args.graph:
+        graphed = GraphedDecodeStep(m, cache, start_pos=0, fused=True,
+                                    fused_linear=args.fused_linear,
+                                    sampler=sampler)
+        graphed.token.copy_(seq[:, 0].contiguous())
+        scalar_steps = graphed.replay
+    else:
+        token = seq[:, 0].contiguous().cuda()
+        pos_dev = torch.zeros((), dtype=torch.long).cuda()
+
+        def scalar_steps(n):
+            for _ in range(n):
+                logits = forward_step_fused(m, token, cache, pos_dev,
+                                            fused_linear=args.fused_linear)
+                sampler.sample(logits, pos_dev, token)
+                pos_dev.add_(1)
+
+    def scalar_block(n):
+        done = 0
+        while done < n:
+            c = min(args.check_every, n - done)
+            scalar_steps(c)
+            done += c
+            sampler.pads.cpu()
+        return done
+
+    engine = SlotEngine(m, B, graph=args.graph,
+                        fused_linear=args.fused_linear,
+                        check_every=args.check_every)
+    engine.submit(list(primes), m.cfg.seq_len, top_k=args.top_k or None,
+                  seed=seed)
+
+    def slot_block(n):
+        # whole engine cycles: up to check_every - 1 steps more than n
+        start = engine.steps
+        while engine.steps - start < n:
+            engine.cycle()
+        return engine.steps - start
+
+    def timed(block, n):
+        """ms per step over the steps the block really ran."""
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ran = block(n)
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0) / ran
+
+    scalar_block(args.warmup)
+    slot_block(args.warmup)
+    scalar, slot = [], []
+    for _ in range(args.repeats):
+        scalar.append(timed(scalar_block, T))
+        slot.append(timed(slot_block, T))
+    mode = ("graphed" if args.graph else "eager") + "+fused" + \
+        ("+linear" if args.fused_linear else "") + \
+        f"+devsample/{args.check_every}" + \
+        (f"+top{args.top_k}" if args.top_k else "")
+    print(f"step[{mode}, batch {B}] scalar position: {_spread(scalar)} "
+          f"ms/step; slot positions: {_spread(slot)} ms/step "
+          f"({args.repeats} alternating blocks of {T} steps; ProGen-1.2B "
+          "flagship config, bf16)")
+    return statistics.median(scalar), statistics.median(slot)
+
+
+def slot_workload(args, seq_len):
+    """The --requests workload: (prime, length) per request, seeded. Prime
+    lengths 4..64, lengths 64..512 and never past seq_len."""
+    g = torch.Generator().manual_seed(args.seed)
+    out = []
+    for _ in range(args.requests):
+        n = int(torch.randint(4, 65, (1,), generator=g))
+        length = min(int(torch.randint(64, 513, (1,), generator=g)), seq_len)
+        length = max(length, n + 1)
+        out.append((torch.randint(1, 256, (n,), generator=g), length))
+    return out
+
+
+def run_slot_workload(m, args):
+    """Serve the workload once, every request waiting at time 0; returns
+    (wall seconds, generated tokens/s). ``--slots 0``: one
+    ``sample_cached_batch`` per request in sequence, its cache and capture
+    included, as serve.py runs them under its lock."""
+    with torch.no_grad():
+        m.to_logits.bias[0] = -1e4   # every request runs to its length
+    work = slot_workload(args, m.cfg.seq_len)
+    generated = sum(length - len(p) for p, length in work)
+    top_k = args.top_k or None
+    seeds = [args.seed + i for i in range(len(work))] if top_k else \
+        [None] * len(work)
+    latency = []
+    occupancy = None
+    if args.slots:
+        engine = SlotEngine(m, args.slots, graph=args.graph,
+                            fused_linear=args.fused_linear,
+                            check_every=args.check_every)
+        # the engine's one cache and capture belong to the server's start,
+        # not to a request: built before the clock starts and reported apart
+        # (the sequential arm pays a cache and a capture inside every request)
+        torch.cuda.synchronize()
+        tb = time.perf_counter()
+        engine.generate([work[0][0]], len(work[0][0]) + 2, top_k=top_k,
+                        seed=seeds[0])
+        torch.cuda.synchronize()
+        build_s = time.perf_counter() - tb
+        steps0, occ0 = engine.steps, engine.occupied_slot_steps
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        tickets = [engine.submit([p], length, top_k=top_k, seed=s)
+                   for (p, length), s in zip(work, seeds)]
+        engine.run_until_idle()
+        wall = time.perf_counter() - t0
+        for t, (p, length) in zip(tickets, work):
+            assert bool((t.wait() != 0).all()), "a request ended early"
+            latency.append(t.finished - t0)
+        occupancy = (engine.occupied_slot_steps - occ0) / \
+            ((engine.steps - steps0) * args.slots)
+    else:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for (p, length), s in zip(work, seeds):
+            out = sample_cached_batch(
+                m, [p], length, top_k=top_k, graph=args.graph, fused=True,
+                fused_linear=args.fused_linear, device_sampling=True, seed=s,
+                check_every=args.check_every)
+            assert bool((out != 0).all()), "a request ended early"
+            latency.append(time.perf_counter() - t0)
+        wall = time.perf_counter() - t0
+    latency.sort()
+    p50 = latency[len(latency) // 2]
+    p95 = latency[min(len(latency) - 1, int(0.95 * len(latency)))]
+    mode = ("graphed" if args.graph else "eager") + "+fused" + \
+        ("+linear" if args.fused_linear else "") + \
+        (f"+top{args.top_k}" if args.top_k else "")
+    arm = f"engine, {args.slots} slots" if args.slots else \
+        "one request at a time"
+    occ = "" if occupancy is None else \
+        (f", mean slot occupancy {occupancy:.2f}; engine build + capture + "
+         f"first request {build_s:.2f} s, not in the wall time")
+    print(f"workload[{mode}; {arm}]: {len(work)} requests, {generated} "
+          f"generated tokens in {wall:.2f} s -> {generated / wall:.1f} tok/s, "
+          f"latency p50 {p50:.2f} s p95 {p95:.2f} s{occ} "
+          "(ProGen-1.2B flagship config, bf16)")
+    return wall, generated / wall
+
+
 def main():
     args = parse_args()
-    if args.prime_len:
+    if args.slots is not None:
+        if args.requests:
+            run_slot_workload(flagship(), args)
+        else:
+            run_slot_step(flagship(), args)
+    elif args.prime_len:
         run_prime(flagship(), args)
     else:
         run(flagship(), args)
