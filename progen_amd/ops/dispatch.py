@@ -17,239 +17,98 @@ from __future__ import annotations
 
 import importlib
 import os
-from typing import Any, Optional
+from typing import Any, Dict
 
-_EXT: Optional[Any] = None
-_EXT_ERR: Optional[str] = None
-_TRIED = False
+# Short key -> module name of every HIP extension. There are several modules,
+# not one, because each module's export list is pinned by its contract test
+# (tests/*_ext_contract.py assert that no entry point leaks into another
+# module), so a new group of kernels comes as a module of its own. Adding one
+# takes: a line here, a line with its sources in setup.py's EXTENSIONS, a
+# bindings file under ops/hip/, an ``ext_*`` / ``has_ext_*`` pair below, and
+# its contract test. __graft_entry__.build imports every module listed here.
+EXTENSIONS = {
+    "main": "progen_amd._C",
+    "decode": "progen_amd._C_decode",
+    "decode_linear": "progen_amd._C_decode_linear",
+    "decode_sample": "progen_amd._C_decode_sample",
+    "prefill": "progen_amd._C_prefill",
+    "decode_slots": "progen_amd._C_decode_slots",
+}
+
+# key -> the imported module, or the import error as a string; an import,
+# failed or not, is tried once per process
+_LOADED: Dict[str, Any] = {}
 
 
-def _try_load() -> None:
-    global _EXT, _EXT_ERR, _TRIED
-    if _TRIED:
-        return
-    _TRIED = True
-    try:
-        _EXT = importlib.import_module("progen_amd._C")
-    except Exception as e:  # noqa: BLE001 - record and re-raise on GPU use
-        _EXT = None
-        _EXT_ERR = f"{type(e).__name__}: {e}"
+def _available(key: str) -> bool:
+    if key not in _LOADED:
+        try:
+            _LOADED[key] = importlib.import_module(EXTENSIONS[key])
+        except Exception as e:  # noqa: BLE001 - record and re-raise on GPU use
+            _LOADED[key] = f"{type(e).__name__}: {e}"
+    return not isinstance(_LOADED[key], str)
 
 
-def ext() -> Any:
-    """Return the loaded HIP extension, raising loudly if unavailable.
+def _load(key: str) -> Any:
+    """Return the loaded extension, raising loudly if unavailable.
 
     Called only on the GPU path; a GPU box without the built extension is
     a deployment error, never a silent eager fallback."""
-    _try_load()
-    if _EXT is None:
+    if not _available(key):
         raise RuntimeError(
-            "progen_amd HIP extension (progen_amd._C) is not available "
-            f"(import error: {_EXT_ERR}). Build it in-tree with "
+            f"progen_amd HIP extension {EXTENSIONS[key]} is not available "
+            f"(import error: {_LOADED[key]}). Build it in-tree with "
             "`python setup.py build_ext --inplace` (PYTORCH_ROCM_ARCH=gfx950)."
         )
-    return _EXT
+    return _LOADED[key]
+
+
+def ext() -> Any:
+    return _load("main")
 
 
 def has_ext() -> bool:
-    _try_load()
-    return _EXT is not None
-
-
-# the decode-step kernels live in a second module (progen_amd._C_decode,
-# ops/hip/decode_bindings.cpp); same policy, loaded on first use
-_EXT_DECODE: Optional[Any] = None
-_EXT_DECODE_ERR: Optional[str] = None
-_TRIED_DECODE = False
-
-
-def _try_load_decode() -> None:
-    global _EXT_DECODE, _EXT_DECODE_ERR, _TRIED_DECODE
-    if _TRIED_DECODE:
-        return
-    _TRIED_DECODE = True
-    try:
-        _EXT_DECODE = importlib.import_module("progen_amd._C_decode")
-    except Exception as e:  # noqa: BLE001 - record and re-raise on GPU use
-        _EXT_DECODE = None
-        _EXT_DECODE_ERR = f"{type(e).__name__}: {e}"
+    return _available("main")
 
 
 def ext_decode() -> Any:
-    """Return the loaded decode-kernel extension, raising loudly if
-    unavailable — the fused decode step never falls back to torch ops."""
-    _try_load_decode()
-    if _EXT_DECODE is None:
-        raise RuntimeError(
-            "progen_amd decode extension (progen_amd._C_decode) is not "
-            f"available (import error: {_EXT_DECODE_ERR}). Build it in-tree "
-            "with `python setup.py build_ext --inplace` "
-            "(PYTORCH_ROCM_ARCH=gfx950)."
-        )
-    return _EXT_DECODE
+    return _load("decode")
 
 
 def has_ext_decode() -> bool:
-    _try_load_decode()
-    return _EXT_DECODE is not None
-
-
-# the decode step's linear op with fused epilogues: a third module
-# (progen_amd._C_decode_linear, ops/hip/decode_linear_bindings.cpp)
-_EXT_DECODE_LINEAR: Optional[Any] = None
-_EXT_DECODE_LINEAR_ERR: Optional[str] = None
-_TRIED_DECODE_LINEAR = False
-
-
-def _try_load_decode_linear() -> None:
-    global _EXT_DECODE_LINEAR, _EXT_DECODE_LINEAR_ERR, _TRIED_DECODE_LINEAR
-    if _TRIED_DECODE_LINEAR:
-        return
-    _TRIED_DECODE_LINEAR = True
-    try:
-        _EXT_DECODE_LINEAR = importlib.import_module(
-            "progen_amd._C_decode_linear")
-    except Exception as e:  # noqa: BLE001 - record and re-raise on GPU use
-        _EXT_DECODE_LINEAR = None
-        _EXT_DECODE_LINEAR_ERR = f"{type(e).__name__}: {e}"
+    return _available("decode")
 
 
 def ext_decode_linear() -> Any:
-    """Return the loaded decode-linear extension, raising loudly if
-    unavailable — a shape routed to the kernel never falls back."""
-    _try_load_decode_linear()
-    if _EXT_DECODE_LINEAR is None:
-        raise RuntimeError(
-            "progen_amd decode-linear extension "
-            "(progen_amd._C_decode_linear) is not available (import error: "
-            f"{_EXT_DECODE_LINEAR_ERR}). Build it in-tree with "
-            "`python setup.py build_ext --inplace` "
-            "(PYTORCH_ROCM_ARCH=gfx950)."
-        )
-    return _EXT_DECODE_LINEAR
+    return _load("decode_linear")
 
 
 def has_ext_decode_linear() -> bool:
-    _try_load_decode_linear()
-    return _EXT_DECODE_LINEAR is not None
-
-
-# the decode step's sampler: a fourth module
-# (progen_amd._C_decode_sample, ops/hip/decode_sample_bindings.cpp)
-_EXT_DECODE_SAMPLE: Optional[Any] = None
-_EXT_DECODE_SAMPLE_ERR: Optional[str] = None
-_TRIED_DECODE_SAMPLE = False
-
-
-def _try_load_decode_sample() -> None:
-    global _EXT_DECODE_SAMPLE, _EXT_DECODE_SAMPLE_ERR, _TRIED_DECODE_SAMPLE
-    if _TRIED_DECODE_SAMPLE:
-        return
-    _TRIED_DECODE_SAMPLE = True
-    try:
-        _EXT_DECODE_SAMPLE = importlib.import_module(
-            "progen_amd._C_decode_sample")
-    except Exception as e:  # noqa: BLE001 - record and re-raise on GPU use
-        _EXT_DECODE_SAMPLE = None
-        _EXT_DECODE_SAMPLE_ERR = f"{type(e).__name__}: {e}"
+    return _available("decode_linear")
 
 
 def ext_decode_sample() -> Any:
-    """Return the loaded decode-sample extension, raising loudly if
-    unavailable — device sampling never falls back to the host sampler."""
-    _try_load_decode_sample()
-    if _EXT_DECODE_SAMPLE is None:
-        raise RuntimeError(
-            "progen_amd decode-sample extension "
-            "(progen_amd._C_decode_sample) is not available (import error: "
-            f"{_EXT_DECODE_SAMPLE_ERR}). Build it in-tree with "
-            "`python setup.py build_ext --inplace` "
-            "(PYTORCH_ROCM_ARCH=gfx950)."
-        )
-    return _EXT_DECODE_SAMPLE
+    return _load("decode_sample")
 
 
 def has_ext_decode_sample() -> bool:
-    _try_load_decode_sample()
-    return _EXT_DECODE_SAMPLE is not None
-
-
-# the kernels that prefill the decode caches from one forward over the
-# prime: a fifth module (progen_amd._C_prefill, ops/hip/prefill_bindings.cpp)
-_EXT_PREFILL: Optional[Any] = None
-_EXT_PREFILL_ERR: Optional[str] = None
-_TRIED_PREFILL = False
-
-
-def _try_load_prefill() -> None:
-    global _EXT_PREFILL, _EXT_PREFILL_ERR, _TRIED_PREFILL
-    if _TRIED_PREFILL:
-        return
-    _TRIED_PREFILL = True
-    try:
-        _EXT_PREFILL = importlib.import_module("progen_amd._C_prefill")
-    except Exception as e:  # noqa: BLE001 - record and re-raise on GPU use
-        _EXT_PREFILL = None
-        _EXT_PREFILL_ERR = f"{type(e).__name__}: {e}"
+    return _available("decode_sample")
 
 
 def ext_prefill() -> Any:
-    """Return the loaded prefill extension, raising loudly if unavailable —
-    a prefill on a GPU never falls back to torch ops."""
-    _try_load_prefill()
-    if _EXT_PREFILL is None:
-        raise RuntimeError(
-            "progen_amd prefill extension (progen_amd._C_prefill) is not "
-            f"available (import error: {_EXT_PREFILL_ERR}). Build it in-tree "
-            "with `python setup.py build_ext --inplace` "
-            "(PYTORCH_ROCM_ARCH=gfx950)."
-        )
-    return _EXT_PREFILL
+    return _load("prefill")
 
 
 def has_ext_prefill() -> bool:
-    _try_load_prefill()
-    return _EXT_PREFILL is not None
-
-
-# the decode kernels with one position per batch row: a sixth module
-# (progen_amd._C_decode_slots, ops/hip/decode_slots_bindings.cpp)
-_EXT_DECODE_SLOTS: Optional[Any] = None
-_EXT_DECODE_SLOTS_ERR: Optional[str] = None
-_TRIED_DECODE_SLOTS = False
-
-
-def _try_load_decode_slots() -> None:
-    global _EXT_DECODE_SLOTS, _EXT_DECODE_SLOTS_ERR, _TRIED_DECODE_SLOTS
-    if _TRIED_DECODE_SLOTS:
-        return
-    _TRIED_DECODE_SLOTS = True
-    try:
-        _EXT_DECODE_SLOTS = importlib.import_module(
-            "progen_amd._C_decode_slots")
-    except Exception as e:  # noqa: BLE001 - record and re-raise on GPU use
-        _EXT_DECODE_SLOTS = None
-        _EXT_DECODE_SLOTS_ERR = f"{type(e).__name__}: {e}"
+    return _available("prefill")
 
 
 def ext_decode_slots() -> Any:
-    """Return the loaded slot-kernel extension, raising loudly if
-    unavailable — the slot step never falls back to torch ops."""
-    _try_load_decode_slots()
-    if _EXT_DECODE_SLOTS is None:
-        raise RuntimeError(
-            "progen_amd decode-slots extension "
-            "(progen_amd._C_decode_slots) is not available (import error: "
-            f"{_EXT_DECODE_SLOTS_ERR}). Build it in-tree with "
-            "`python setup.py build_ext --inplace` "
-            "(PYTORCH_ROCM_ARCH=gfx950)."
-        )
-    return _EXT_DECODE_SLOTS
+    return _load("decode_slots")
 
 
 def has_ext_decode_slots() -> bool:
-    _try_load_decode_slots()
-    return _EXT_DECODE_SLOTS is not None
+    return _available("decode_slots")
 
 
 def use_hip(t, op: str = None) -> bool:

@@ -1,11 +1,12 @@
 // PyTorch bindings for the slot kernels (progen_amd._C_decode_slots).
 //
-// A sixth extension module, because the export lists of the other five are
-// pinned: the decode-step kernels with one position per batch row
-// (decode_slots.hip), for a decode batch whose rows serve different requests
-// (progen_amd/engine.py). Entry points follow the launch contract of
-// checks.h: dtype, shape/contiguity, divisibility, range and device checks in
-// that order, then DeviceScope, allocation and LAUNCH.
+// The decode-step kernels with one position per batch row (decode_slots.hip),
+// for a decode batch whose rows serve different requests
+// (progen_amd/engine.py). The checked entries of the three kernels shared
+// with the scalar step are in decode_entries.h; the functions here are its
+// SLOTS = true instances. The sampler's entry is this file's own and follows
+// the launch contract of checks.h: dtype, shape/contiguity, divisibility,
+// range and device checks in that order, then DeviceScope and LAUNCH.
 //
 // ``pos`` is a (B,) int64 DEVICE tensor; pos[b] < 0 marks an idle row. Its
 // values, like those of the sampler's ``ctl``, cannot be checked here without
@@ -14,8 +15,7 @@
 
 #include <torch/extension.h>
 
-#include "checks.h"
-#include "decode_slots_kernels.h"
+#include "decode_entries.h"
 
 using namespace chk;
 
@@ -26,35 +26,8 @@ at::Tensor dec_ln_shift_slots(at::Tensor h,
                               const at::Tensor& g,
                               const c10::optional<at::Tensor>& prev,
                               const at::Tensor& pos, bool shift, double eps) {
-  const char* op = "dec_ln_shift_slots";
-  const bool bf = dtype_bf16_or_fp32(op, ARG(h));
-  if (res) dtype_same(op, Arg{"res", *res}, ARG(h));
-  dtype_same(op, ARG(g), ARG(h));
-  if (prev) dtype_same(op, Arg{"prev", *prev}, ARG(h));
-  dtype_is(op, ARG(pos), at::kLong);
-  contiguous_rank(op, ARG(h), 2);
-  const int64_t B = h.size(0), D = h.size(1);
-  if (res) contiguous_shape(op, Arg{"res", *res}, h.sizes());
-  contiguous_numel(op, ARG(g), D);
-  if (prev) contiguous_shape(op, Arg{"prev", *prev}, h.sizes());
-  contiguous_shape(op, ARG(pos), {B});
-  CHK(prev.has_value() || !shift, op, "prev", "None", "must be given when shift is set");
-  // the shifted half D/2 must be whole 8-element chunks
-  multiple_of(op, "D", D, 16);
-  const int Bi = extent_int(op, "B", B, kGridYZ);
-  const int Di = extent_int(op, "D", D);
-  same_gpu(op, {ARG(h), ARG(g), ARG(pos)});
-  if (res) same_gpu(op, {ARG(h), Arg{"res", *res}});
-  if (prev) same_gpu(op, {ARG(h), Arg{"prev", *prev}});
-
-  DeviceScope dev(h);
-  auto y = at::empty_like(h);
-  LAUNCH(op, dec_ln_shift_slots_launch(
-                 h.data_ptr(), res ? res->data_ptr() : nullptr, g.data_ptr(),
-                 prev ? prev->data_ptr() : nullptr, y.data_ptr(),
-                 (const long long*)pos.data_ptr<int64_t>(), Bi, Di, (float)eps,
-                 shift, bf, dev.stream));
-  return y;
+  return dec::ln_shift<true>("dec_ln_shift_slots", h, res, g, prev, &pos,
+                             shift, eps);
 }
 
 // dec_attn with a position per row: rotary, cache write and band at pos[b];
@@ -63,39 +36,8 @@ at::Tensor dec_attn_slots(const at::Tensor& qkv, const at::Tensor& rsin,
                           const at::Tensor& rcos, const at::Tensor& pos,
                           at::Tensor k_cache, at::Tensor v_cache,
                           int64_t window) {
-  const char* op = "dec_attn_slots";
-  const int wsz = extent_int(op, "window", window);
-  const bool bf = dtype_bf16_or_fp32(op, ARG(qkv));
-  dtype_is(op, ARG(rsin), at::kFloat);
-  dtype_is(op, ARG(rcos), at::kFloat);
-  dtype_is(op, ARG(pos), at::kLong);
-  dtype_same(op, ARG(k_cache), ARG(qkv));
-  dtype_same(op, ARG(v_cache), ARG(qkv));
-  contiguous_rank(op, ARG(k_cache), 4);
-  const int64_t B = k_cache.size(0), H = k_cache.size(1), N = k_cache.size(2);
-  CHK(k_cache.size(3) == 64, op, "k_cache", k_cache.sizes(),
-      "must have shape (B, H, N, 64)");
-  contiguous_shape(op, ARG(v_cache), k_cache.sizes());
-  contiguous_shape(op, ARG(qkv), {B, 3 * H * 64});
-  rope_table(op, ARG(rsin), N);
-  rope_table(op, ARG(rcos), N);
-  contiguous_shape(op, ARG(pos), {B});
-  multiple_of(op, "window", window, 64);
-  multiple_of(op, "N", N, window);
-  const int BH = extent_int(op, "B*H", B * H, kGridYZ);
-  const int Ni = extent_int(op, "N", N);
-  same_gpu(op, {ARG(qkv), ARG(rsin), ARG(rcos), ARG(pos), ARG(k_cache),
-                ARG(v_cache)});
-
-  DeviceScope dev(qkv);
-  auto out = at::empty({B, H * 64}, qkv.options());
-  LAUNCH(op, dec_attn_slots_launch(
-                 qkv.data_ptr(), rsin.data_ptr<float>(),
-                 rcos.data_ptr<float>(),
-                 (const long long*)pos.data_ptr<int64_t>(), k_cache.data_ptr(),
-                 v_cache.data_ptr(), out.data_ptr(), BH / (int)H, (int)H, Ni,
-                 wsz, bf, dev.stream));
-  return out;
+  return dec::attn<true>("dec_attn_slots", qkv, rsin, rcos, pos, k_cache,
+                         v_cache, window);
 }
 
 // dec_sgu with a position per row: history write and causal row at pos[b];
@@ -104,34 +46,7 @@ at::Tensor dec_sgu_slots(const at::Tensor& h, const at::Tensor& g,
                          at::Tensor hist, const at::Tensor& w,
                          const at::Tensor& bias, const at::Tensor& pos,
                          double eps) {
-  const char* op = "dec_sgu_slots";
-  const bool bf = dtype_bf16_or_fp32(op, ARG(h));
-  dtype_same(op, ARG(g), ARG(h));
-  dtype_same(op, ARG(hist), ARG(h));
-  dtype_same(op, ARG(w), ARG(h));
-  dtype_same(op, ARG(bias), ARG(h));
-  dtype_is(op, ARG(pos), at::kLong);
-  contiguous_rank(op, ARG(hist), 3);
-  const int64_t B = hist.size(0), N = hist.size(1), d2 = hist.size(2);
-  contiguous_shape(op, ARG(h), {B, 2 * d2});
-  contiguous_numel(op, ARG(g), d2);
-  contiguous_shape(op, ARG(w), {N, N});
-  contiguous_shape(op, ARG(bias), {N, 1});
-  contiguous_shape(op, ARG(pos), {B});
-  multiple_of(op, "d2", d2, 64);  // one workgroup per 64-column tile
-  const int Bi = extent_int(op, "B", B, kGridYZ);
-  const int Ni = extent_int(op, "N", N);
-  const int d2i = extent_int(op, "d2", d2);
-  same_gpu(op, {ARG(h), ARG(g), ARG(hist), ARG(w), ARG(bias), ARG(pos)});
-
-  DeviceScope dev(h);
-  auto out = at::empty({B, d2}, h.options());
-  LAUNCH(op, dec_sgu_slots_launch(h.data_ptr(), g.data_ptr(), hist.data_ptr(),
-                                  w.data_ptr(), bias.data_ptr(),
-                                  (const long long*)pos.data_ptr<int64_t>(),
-                                  out.data_ptr(), Bi, Ni, d2i, (float)eps, bf,
-                                  dev.stream));
-  return out;
+  return dec::sgu<true>("dec_sgu_slots", h, g, hist, w, bias, pos, eps);
 }
 
 // dec_sample with a position and a control row [len, limit, top_k, seed,

@@ -1,7 +1,5 @@
-"""In-tree build of the progen_amd._C, progen_amd._C_decode,
-progen_amd._C_decode_linear, progen_amd._C_decode_sample,
-progen_amd._C_prefill and progen_amd._C_decode_slots HIP extensions (gfx950
-only).
+"""In-tree build of the progen_amd._C* HIP extensions listed in EXTENSIONS
+(gfx950 only).
 
     PYTORCH_ROCM_ARCH=gfx950 python setup.py build_ext --inplace
 
@@ -18,56 +16,53 @@ os.environ.setdefault("PYTORCH_ROCM_ARCH", "gfx950")
 
 from torch.utils.cpp_extension import BuildExtension, CUDAExtension  # noqa: E402
 
-HIP_SOURCES = [
-    "progen_amd/ops/hip/bindings.cpp",
-    "progen_amd/ops/hip/ln_shift.hip",
-    "progen_amd/ops/hip/glu.hip",
-    "progen_amd/ops/hip/cross_entropy.hip",
-    "progen_amd/ops/hip/adamw.hip",
-    "progen_amd/ops/hip/rope_qkv.hip",
-    "progen_amd/ops/hip/attention_fwd.hip",
-    "progen_amd/ops/hip/attention_bwd.hip",
-    "progen_amd/ops/hip/sgu.hip",
-    "progen_amd/ops/hip/fp8_quant.hip",
-    "progen_amd/ops/hip/colsum.hip",
-]
-
-# the fused kernels of the cached decode step (progen_amd/decode.py);
-# a module of its own so that progen_amd._C keeps its exact export list
-DECODE_SOURCES = [
-    "progen_amd/ops/hip/decode_bindings.cpp",
-    "progen_amd/ops/hip/decode_ln_shift.hip",
-    "progen_amd/ops/hip/decode_attn.hip",
-    "progen_amd/ops/hip/decode_sgu.hip",
-]
-
-# the decode step's linear op with fused epilogues; a third module, because
-# the export lists of the two above are pinned
-DECODE_LINEAR_SOURCES = [
-    "progen_amd/ops/hip/decode_linear_bindings.cpp",
-    "progen_amd/ops/hip/decode_linear.hip",
-]
-
-# the decode step's sampler; a fourth module for the same reason
-DECODE_SAMPLE_SOURCES = [
-    "progen_amd/ops/hip/decode_sample_bindings.cpp",
-    "progen_amd/ops/hip/decode_sample.hip",
-]
-
-# the kernels that fill the decode caches from one forward over the prime; a
-# fifth module for the same reason
-PREFILL_SOURCES = [
-    "progen_amd/ops/hip/prefill_bindings.cpp",
-    "progen_amd/ops/hip/prefill.hip",
-]
-
-# the decode kernels with one position per batch row (progen_amd/engine.py);
-# a sixth module for the same reason. The kernel bodies are the
-# decode_*_body.h headers shared with the four scalar kernels above
-DECODE_SLOTS_SOURCES = [
-    "progen_amd/ops/hip/decode_slots_bindings.cpp",
-    "progen_amd/ops/hip/decode_slots.hip",
-]
+# Module name -> sources. Several modules, not one: the export list of each
+# is pinned by its contract test (see EXTENSIONS in progen_amd/ops/dispatch.py,
+# which lists the same names and says what adding a module takes). The bodies
+# of the decode kernels are the decode_*_body.h headers, shared by the scalar
+# kernels and decode_slots.hip.
+EXTENSIONS = {
+    "progen_amd._C": [
+        "progen_amd/ops/hip/bindings.cpp",
+        "progen_amd/ops/hip/ln_shift.hip",
+        "progen_amd/ops/hip/glu.hip",
+        "progen_amd/ops/hip/cross_entropy.hip",
+        "progen_amd/ops/hip/adamw.hip",
+        "progen_amd/ops/hip/rope_qkv.hip",
+        "progen_amd/ops/hip/attention_fwd.hip",
+        "progen_amd/ops/hip/attention_bwd.hip",
+        "progen_amd/ops/hip/sgu.hip",
+        "progen_amd/ops/hip/fp8_quant.hip",
+        "progen_amd/ops/hip/colsum.hip",
+    ],
+    # the fused kernels of the cached decode step (progen_amd/decode.py)
+    "progen_amd._C_decode": [
+        "progen_amd/ops/hip/decode_bindings.cpp",
+        "progen_amd/ops/hip/decode_ln_shift.hip",
+        "progen_amd/ops/hip/decode_attn.hip",
+        "progen_amd/ops/hip/decode_sgu.hip",
+    ],
+    # the decode step's linear op with fused epilogues
+    "progen_amd._C_decode_linear": [
+        "progen_amd/ops/hip/decode_linear_bindings.cpp",
+        "progen_amd/ops/hip/decode_linear.hip",
+    ],
+    # the decode step's sampler
+    "progen_amd._C_decode_sample": [
+        "progen_amd/ops/hip/decode_sample_bindings.cpp",
+        "progen_amd/ops/hip/decode_sample.hip",
+    ],
+    # the kernels that fill the decode caches from one forward over the prime
+    "progen_amd._C_prefill": [
+        "progen_amd/ops/hip/prefill_bindings.cpp",
+        "progen_amd/ops/hip/prefill.hip",
+    ],
+    # the decode kernels with one position per batch row (progen_amd/engine.py)
+    "progen_amd._C_decode_slots": [
+        "progen_amd/ops/hip/decode_slots_bindings.cpp",
+        "progen_amd/ops/hip/decode_slots.hip",
+    ],
+}
 
 # Headers the .hip sources include (the decode kernel bodies among them are
 # shared by five of the files above). The ninja rule generated for .hip
@@ -95,42 +90,9 @@ COMPILE_ARGS = {
 setup(
     name="progen_amd_ext",
     ext_modules=[
-        CUDAExtension(
-            name="progen_amd._C",
-            sources=HIP_SOURCES,
-            extra_compile_args=COMPILE_ARGS,
-            depends=HIP_HEADERS,
-        ),
-        CUDAExtension(
-            name="progen_amd._C_decode",
-            sources=DECODE_SOURCES,
-            extra_compile_args=COMPILE_ARGS,
-            depends=HIP_HEADERS,
-        ),
-        CUDAExtension(
-            name="progen_amd._C_decode_linear",
-            sources=DECODE_LINEAR_SOURCES,
-            extra_compile_args=COMPILE_ARGS,
-            depends=HIP_HEADERS,
-        ),
-        CUDAExtension(
-            name="progen_amd._C_decode_sample",
-            sources=DECODE_SAMPLE_SOURCES,
-            extra_compile_args=COMPILE_ARGS,
-            depends=HIP_HEADERS,
-        ),
-        CUDAExtension(
-            name="progen_amd._C_prefill",
-            sources=PREFILL_SOURCES,
-            extra_compile_args=COMPILE_ARGS,
-            depends=HIP_HEADERS,
-        ),
-        CUDAExtension(
-            name="progen_amd._C_decode_slots",
-            sources=DECODE_SLOTS_SOURCES,
-            extra_compile_args=COMPILE_ARGS,
-            depends=HIP_HEADERS,
-        ),
+        CUDAExtension(name=name, sources=sources,
+                      extra_compile_args=COMPILE_ARGS, depends=HIP_HEADERS)
+        for name, sources in EXTENSIONS.items()
     ],
     cmdclass={"build_ext": BuildHip.with_options(use_ninja=True)},
 )

@@ -12,15 +12,9 @@ no skip).
 """
 
 import pytest
-import torch
 
+from ext_contract_helpers import F16, F32, raises_first_line, t
 from progen_amd.ops import dispatch
-
-BF, F16, F32 = torch.bfloat16, torch.float16, torch.float32
-
-
-def t(*shape, dtype=BF):
-    return torch.zeros(*shape, dtype=dtype)
 
 
 # The well-formed call, arguments in positional order: B=2, K=64, N=32.
@@ -69,12 +63,8 @@ BAD = [
 
 
 def _raises(overrides):
-    args = good()
-    assert set(overrides) <= set(args), overrides
-    args.update(overrides)
-    with pytest.raises(RuntimeError) as ei:
-        dispatch.ext_decode_linear().dec_linear(*args.values())
-    return str(ei.value).splitlines()[0]
+    return raises_first_line(dispatch.ext_decode_linear(), good, "dec_linear",
+                             overrides)
 
 
 def test_the_export_set_is_the_one_entry_point():

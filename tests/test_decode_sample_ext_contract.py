@@ -14,19 +14,9 @@ no skip).
 import pytest
 import torch
 
+from ext_contract_helpers import (F16, F32, I32, I64, meta,
+                                  raises_first_line, t)
 from progen_amd.ops import dispatch
-
-BF, F16, F32 = torch.bfloat16, torch.float16, torch.float32
-I32, I64 = torch.int32, torch.int64
-
-
-def t(*shape, dtype=BF):
-    return torch.zeros(*shape, dtype=dtype)
-
-
-def meta(*shape, dtype=BF):
-    """Contiguous tensor of any extent with no storage behind it."""
-    return torch.empty(*shape, dtype=dtype, device="meta")
 
 
 def ints(*shape):
@@ -93,12 +83,8 @@ BAD = [
 
 
 def _raises(overrides):
-    args = good()
-    assert set(overrides) <= set(args), overrides
-    args.update(overrides)
-    with pytest.raises(RuntimeError) as ei:
-        dispatch.ext_decode_sample().dec_sample(*args.values())
-    return str(ei.value).splitlines()[0]
+    return raises_first_line(dispatch.ext_decode_sample(), good, "dec_sample",
+                             overrides)
 
 
 def test_the_export_set_is_the_one_entry_point():

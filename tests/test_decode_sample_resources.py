@@ -9,42 +9,18 @@ here and the table printed.
 """
 
 import os
-import re
-import shutil
-import subprocess
 
 import pytest
+
+from hip_resources import hipcc, kernel_resource_usage
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "..", "progen_amd", "ops", "hip", "decode_sample.hip")
 
 
-def _hipcc():
-    return shutil.which("hipcc") or (
-        "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
-
-
-@pytest.mark.skipif(_hipcc() is None, reason="needs hipcc")
+@pytest.mark.skipif(hipcc() is None, reason="needs hipcc")
 def test_decode_sample_kernels_use_no_scratch(tmp_path):
-    r = subprocess.run(
-        [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17",
-         "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-         "-c", SRC, "-o", str(tmp_path / "decode_sample.o")],
-        capture_output=True, text=True, check=True)
-    usage = {}
-    name = None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-            continue
-        m = re.search(r"remark:\s+(SGPRs|VGPRs|AGPRs|"
-                      r"ScratchSize \[bytes/lane\]|"
-                      r"Occupancy \[waves/SIMD\]|"
-                      r"LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name:
-            usage[name][m.group(1).split(" ")[0]] = int(m.group(2))
+    usage = kernel_resource_usage(SRC, tmp_path)
     # one instantiation per storage type: bf16 and fp32
     kernels = [k for k in usage if "dec_sample_kernel" in k]
     assert len(kernels) == 2, sorted(usage)

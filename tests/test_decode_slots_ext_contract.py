@@ -10,24 +10,14 @@ argument checks are skipped where the extension is not built.
 """
 
 import pytest
-import torch
 
+import test_decode_ext_contract as scalar
+from ext_contract_helpers import (F16, F32, I32, I64, meta,
+                                  raises_first_line, t)
 from progen_amd.ops import dispatch
-
-BF, F16, F32, I64, I32 = (torch.bfloat16, torch.float16, torch.float32,
-                          torch.int64, torch.int32)
 
 needs_ext = pytest.mark.skipif(not dispatch.has_ext_decode_slots(),
                                reason="progen_amd._C_decode_slots is not built")
-
-
-def t(*shape, dtype=BF):
-    return torch.zeros(*shape, dtype=dtype)
-
-
-def meta(*shape, dtype=BF):
-    """Contiguous tensor of any extent with no storage behind it."""
-    return torch.empty(*shape, dtype=dtype, device="meta")
 
 
 # The well-formed calls, arguments in positional order.
@@ -146,12 +136,8 @@ BAD = [
 
 
 def _raises(op, overrides):
-    args = GOOD[op]()
-    assert set(overrides) <= set(args), overrides
-    args.update(overrides)
-    with pytest.raises(RuntimeError) as ei:
-        getattr(dispatch.ext_decode_slots(), op)(*args.values())
-    return str(ei.value).splitlines()[0]
+    return raises_first_line(dispatch.ext_decode_slots(), GOOD[op], op,
+                             overrides)
 
 
 def test_the_export_set_is_the_four_entry_points():
@@ -213,6 +199,50 @@ def test_the_scalar_entry_points_still_refuse_a_1d_pos():
     a.pop("window")
     with pytest.raises(RuntimeError, match="dec_attn: pos must have 0 dims"):
         dispatch.ext_decode().dec_attn(*a.values(), 64)
+
+
+# The scalar step's contract, held against the slot step's. The cases are
+# those of tests/test_decode_ext_contract.py for the three kernels the two
+# steps share, plus each well-formed call; the slot op is called at the SCALAR
+# table's shapes, so that the two messages can be compared whole. Left out:
+# the cases whose override replaces ``pos``, the one argument whose rule
+# differs (0 dims there, (B,) here; the tables above have those).
+SCALAR_ROWS = {"dec_ln_shift": "h", "dec_attn": "k_cache", "dec_sgu": "hist"}
+PARITY = [(op, {}) for op in SCALAR_ROWS] + \
+    [(op, ov) for op, ov, _ in scalar.BAD if "pos" not in ov]
+
+
+def _slot_args_at_scalar_shapes(op, overrides):
+    """The scalar op's well-formed call with ``overrides``, as the slot op
+    takes it: its own argument order, and a (B,) ``pos`` for whatever B the
+    call has."""
+    args = scalar.GOOD[op]()
+    args.update(overrides)
+    args["pos"] = t(args[SCALAR_ROWS[op]].size(0), dtype=I64)
+    names = list(GOOD[op + "_slots"]())
+    assert set(names) == set(args), (names, sorted(args))
+    return {k: args[k] for k in names}
+
+
+def test_parity_cases_cover_each_shared_kernel():
+    for op in SCALAR_ROWS:
+        assert sum(1 for o, ov in PARITY if o == op and ov) >= 3, op
+
+
+@needs_ext
+@pytest.mark.parametrize(
+    "op,overrides", PARITY,
+    ids=[f"{op}-{','.join(ov) or 'full'}-{i}"
+         for i, (op, ov) in enumerate(PARITY)])
+def test_slot_entry_refuses_what_the_scalar_entry_refuses(op, overrides):
+    """Same arguments, same first complaint: the slot op's message is the
+    scalar op's with the op name substituted."""
+    want = scalar._raises(op, overrides)
+    assert want.startswith(f"{op}: "), want
+    got = raises_first_line(
+        dispatch.ext_decode_slots(),
+        lambda: _slot_args_at_scalar_shapes(op, overrides), op + "_slots", {})
+    assert got == f"{op}_slots: " + want[len(op) + 2:], (got, want)
 
 
 @needs_ext

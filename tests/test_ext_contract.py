@@ -14,20 +14,9 @@ be built (``dispatch.ext()`` raises otherwise; no skip).
 import pytest
 import torch
 
+from ext_contract_helpers import (BF, F16, F32, I32, I64, meta,
+                                  raises_first_line, t)
 from progen_amd.ops import dispatch
-
-BF, F16, F32 = torch.bfloat16, torch.float16, torch.float32
-I32, I64 = torch.int32, torch.int64
-
-
-def t(*shape, dtype=BF):
-    return torch.zeros(*shape, dtype=dtype)
-
-
-def meta(*shape, dtype=BF):
-    """Contiguous tensor of any extent with no storage behind it: reaches
-    the range checks that an expanded (non-contiguous) view cannot."""
-    return torch.empty(*shape, dtype=dtype, device="meta")
 
 
 def huge(*shape, dtype=BF):
@@ -289,12 +278,7 @@ BAD = [
 
 
 def _raises(op, overrides):
-    args = GOOD[op]()
-    assert set(overrides) <= set(args), (op, overrides)
-    args.update(overrides)
-    with pytest.raises(RuntimeError) as ei:
-        getattr(dispatch.ext(), op)(*args.values())
-    return str(ei.value).splitlines()[0]
+    return raises_first_line(dispatch.ext(), GOOD[op], op, overrides)
 
 
 def test_every_kernel_entry_point_is_covered():

@@ -10,23 +10,12 @@ argument checks are skipped where the extension is not built.
 """
 
 import pytest
-import torch
 
+from ext_contract_helpers import F16, F32, meta, raises_first_line, t
 from progen_amd.ops import dispatch
-
-BF, F16, F32 = torch.bfloat16, torch.float16, torch.float32
 
 needs_ext = pytest.mark.skipif(not dispatch.has_ext_prefill(),
                                reason="progen_amd._C_prefill is not built")
-
-
-def t(*shape, dtype=BF):
-    return torch.zeros(*shape, dtype=dtype)
-
-
-def meta(*shape, dtype=BF):
-    """Contiguous tensor of any extent with no storage behind it."""
-    return torch.empty(*shape, dtype=dtype, device="meta")
 
 
 # The well-formed calls, arguments in positional order.
@@ -108,12 +97,7 @@ BAD = [
 
 
 def _raises(op, overrides):
-    args = GOOD[op]()
-    assert set(overrides) <= set(args), overrides
-    args.update(overrides)
-    with pytest.raises(RuntimeError) as ei:
-        getattr(dispatch.ext_prefill(), op)(*args.values())
-    return str(ei.value).splitlines()[0]
+    return raises_first_line(dispatch.ext_prefill(), GOOD[op], op, overrides)
 
 
 def test_the_export_set_is_the_two_entry_points():

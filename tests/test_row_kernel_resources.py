@@ -15,10 +15,10 @@ never fall below).
 
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
+
+from hip_resources import hipcc, kernel_resource_usage
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 HIP = os.path.join(HERE, "..", "progen_amd", "ops", "hip")
@@ -40,37 +40,10 @@ LN_BWD_FLOOR = {
 }
 
 
-def _hipcc():
-    return shutil.which("hipcc") or (
-        "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
-
-
-def _usage(name, tmp_path):
-    r = subprocess.run(
-        [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17",
-         "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-         "-c", os.path.join(HIP, name + ".hip"),
-         "-o", str(tmp_path / (name + ".o"))],
-        capture_output=True, text=True, check=True)
-    usage = {}
-    sym = None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            sym = m.group(1)
-            usage[sym] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|"
-                      r"Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and sym:
-            usage[sym][m.group(1).split(" ")[0]] = int(m.group(2))
-    return usage
-
-
-@pytest.mark.skipif(_hipcc() is None, reason="needs hipcc")
+@pytest.mark.skipif(hipcc() is None, reason="needs hipcc")
 @pytest.mark.parametrize("name", sorted(KERNELS))
 def test_row_kernels_keep_their_occupancy_without_scratch(name, tmp_path):
-    usage = _usage(name, tmp_path)
+    usage = kernel_resource_usage(os.path.join(HIP, name + ".hip"), tmp_path)
     for kernel, count in KERNELS[name].items():
         assert sum(kernel in k for k in usage) == count, (kernel, sorted(usage))
     assert len(usage) == sum(KERNELS[name].values()), sorted(usage)
