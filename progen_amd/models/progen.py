@@ -26,6 +26,7 @@ from typing import Any, Dict, Optional
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from ..config import ProGenConfig
 from ..ops import functional as OF
@@ -62,6 +63,21 @@ class Linear(nn.Linear):
         return overlap_linear(x, self.weight, self.bias)
 
 
+def linear_handing_bias_on(lin: nn.Module, x: torch.Tensor, consumer: str):
+    """``lin(x)`` for a linear whose output goes next to the op ``consumer``
+    ("glu" / "ln"), which can deliver the linear's bias gradient from its own
+    backward kernel. Returns ``(y, bias)``. Where ``OF.fused_dbias`` holds,
+    ``bias`` is the parameter to hand to that op, and the GEMM ran with it
+    detached: the forward is the same (GEMM with the bias epilogue) and
+    torch's linear_backward skips its column reduce. Otherwise ``bias`` is
+    None and the linear computes its bias gradient itself; so does any
+    module that is not this file's ``Linear`` (the tensor-parallel ones)."""
+    if type(lin) is Linear and OF.fused_dbias(x, lin.weight, lin.bias,
+                                              consumer):
+        return F.linear(x, lin.weight, lin.bias.detach()), lin.bias
+    return lin(x), None
+
+
 class LocalAttention(nn.Module):
     """Windowed causal attention with one-window lookback
     (reference: progen.py:50-103)."""
@@ -80,12 +96,23 @@ class LocalAttention(nn.Module):
         x = OF.ln_shift(x, self.norm_weight, shift=self.shift_tokens)
         return self.inner(x, sin, cos)
 
+    def _context(self, y: torch.Tensor, sin: torch.Tensor,
+                 cos: torch.Tensor) -> torch.Tensor:
+        qkv = self.to_qkv(y)
+        return OF.local_attention(qkv, sin, cos, self.heads, self.window_size)
+
     def inner(self, y: torch.Tensor, sin: torch.Tensor, cos: torch.Tensor) -> torch.Tensor:
         """Branch body AFTER the LN+shift prologue (the prologue is fused
         with the residual add in ProGenBase.forward)."""
-        qkv = self.to_qkv(y)
-        out = OF.local_attention(qkv, sin, cos, self.heads, self.window_size)
-        return self.to_out(out)
+        return self.to_out(self._context(y, sin, cos))
+
+    def inner_with_bias(self, y: torch.Tensor, sin: torch.Tensor,
+                        cos: torch.Tensor, consumer: str):
+        """``inner`` for a caller that hands the result to the op ``consumer``
+        next: always the pair ``(out, bias)`` of ``linear_handing_bias_on`` for
+        ``to_out``, and the caller must pass ``bias`` on to that op."""
+        return linear_handing_bias_on(self.to_out, self._context(y, sin, cos),
+                                      consumer)
 
 
 class SGU(nn.Module):
@@ -130,16 +157,30 @@ class FeedForward(nn.Module):
         x = OF.ln_shift(x, self.norm_weight, shift=self.shift_tokens)
         return self.inner(x)
 
-    def inner(self, x: torch.Tensor) -> torch.Tensor:
-        """Branch body AFTER the LN+shift prologue (see LocalAttention.inner)."""
-        x = self.proj_in(x)
+    def _hidden(self, x: torch.Tensor) -> torch.Tensor:
+        """Everything before ``proj_out``. In a GLU layer, on every route
+        (``forward``, ``inner``, ``inner_with_bias``) where ``OF.fused_dbias``
+        holds, ``proj_in`` runs with its bias detached and ``glu_gelu``
+        delivers that bias's gradient."""
         if self.glu:
-            x = OF.glu_gelu(x)
+            # glu_gelu's backward stores proj_in's output gradient and sums
+            # it for proj_in.bias on the way
+            x, bias = linear_handing_bias_on(self.proj_in, x, "glu")
+            x = OF.glu_gelu(x, bias)
         else:
-            x = OF.gelu(x)
+            x = OF.gelu(self.proj_in(x))
         if self.sgu is not None:
             x = self.sgu(x)
-        return self.proj_out(x)
+        return x
+
+    def inner(self, x: torch.Tensor) -> torch.Tensor:
+        """Branch body AFTER the LN+shift prologue (see LocalAttention.inner)."""
+        return self.proj_out(self._hidden(x))
+
+    def inner_with_bias(self, x: torch.Tensor, consumer: str):
+        """``inner`` returning the pair ``(out, bias)`` for ``proj_out`` (see
+        LocalAttention.inner_with_bias)."""
+        return linear_handing_bias_on(self.proj_out, self._hidden(x), consumer)
 
 
 class ProGenBase(nn.Module):
@@ -186,16 +227,21 @@ class ProGenBase(nn.Module):
         # (ops/hip/ln_shift.hip RES variant): ln_shift_res(h, r) returns
         # the LN'd branch input AND the updated residual stream h + r,
         # so `h = h + branch(h)` never runs as a separate pass
+        # Each branch's last linear (to_out, ff.proj_out) hands its bias on
+        # with its output where the next ln_shift_res delivers that bias's
+        # gradient (OF.fused_dbias): the backward of ln_shift_res stores the
+        # linear's output gradient and sums it on the way.
         h = self.embed(x.long())
-        r = None
+        r = r_bias = None
         for attn, ff in self.layers:
             y, h = OF.ln_shift_res(h, r, attn.norm_weight,
-                                   shift=attn.shift_tokens)
-            a = attn.inner(y, sin, cos)
+                                   shift=attn.shift_tokens, res_bias=r_bias)
+            a, a_bias = attn.inner_with_bias(y, sin, cos, "ln")
             y, h = OF.ln_shift_res(h, a, ff.norm_weight,
-                                   shift=ff.shift_tokens)
-            r = ff.inner(y)
-        y, _ = OF.ln_shift_res(h, r, self.final_norm_weight, shift=False)
+                                   shift=ff.shift_tokens, res_bias=a_bias)
+            r, r_bias = ff.inner_with_bias(y, "ln")
+        y, _ = OF.ln_shift_res(h, r, self.final_norm_weight, shift=False,
+                               res_bias=r_bias)
         return self.to_logits(y)
 
     def num_params(self) -> int:

@@ -12,10 +12,50 @@ also the numerics oracle for the kernels.
 
 from __future__ import annotations
 
+import os
+
 import torch
 import torch.nn.functional as F
 
 from . import dispatch, reference
+
+
+# ---------------------------------------------------------------------------
+# bias gradients taken from the consumer's backward kernel
+# ---------------------------------------------------------------------------
+# The output gradient of a biased linear is summed over its rows for the bias
+# gradient; torch's linear_backward does that with a separate reduce that
+# re-reads the tensor the NEXT backward kernel has just stored. Where that
+# kernel is one of ours (glu_bwd for proj_in, ln_shift_res_bwd for to_out and
+# ff.proj_out) it sums what it stores on the way out (ops/hip/bias_grad.hip).
+# The two halves belong together: the linear is called with a detached bias,
+# so it computes no bias gradient, IF AND ONLY IF its consumer op is handed
+# the bias parameter and delivers the gradient. ``fused_dbias`` is the one
+# predicate that decides both, evaluated once per call site.
+
+def fused_dbias(x: torch.Tensor, weight: torch.Tensor, bias, tag: str) -> bool:
+    """True when the linear ``(weight, bias)`` applied to ``x`` leaves its
+    bias gradient to its consumer op ``tag`` ("glu" or "ln"): the consumer
+    runs its HIP kernel, the linear is torch's own, and
+    ``PROGEN_FUSED_DBIAS`` (read at call time) is not 0."""
+    if bias is None or not bias.requires_grad:
+        return False
+    if os.environ.get("PROGEN_FUSED_DBIAS", "1") == "0":
+        return False
+    if not dispatch.use_hip(x, tag):  # CPU, PROGEN_FORCE_EAGER, PROGEN_EAGER_OPS
+        return False
+    from . import fp8, overlap
+    if fp8.fp8_eligible(x, weight):
+        return False
+    # the custom linear Function computes its own dbias
+    return not (overlap.ENABLED or overlap.FN_LINEAR)
+
+
+def _bias_grad_buffer(bias_dtype, n: int, device):
+    """The fp32 ``db`` a backward kernel fills, or None without a bias."""
+    if bias_dtype is None:
+        return None
+    return torch.empty(n, dtype=torch.float32, device=device)
 
 
 # ---------------------------------------------------------------------------
@@ -54,15 +94,21 @@ class _LnShiftResFn(torch.autograd.Function):
     (y, s) — s is the new residual stream. Backward returns the SAME
     gradient tensor for x and res (d(x+res) fans out identically); both
     are intermediate activations here, never leaves, so sharing is safe
-    and saves the autograd accumulation pass."""
+    and saves the autograd accumulation pass.
+
+    ``res_bias`` (optional) is the bias of the linear that produced ``res``,
+    unused in forward: dx is that linear's output gradient, so the backward
+    kernel also sums it per column and the sum is returned as the bias's
+    gradient (see ``fused_dbias``)."""
 
     @staticmethod
-    def forward(ctx, x, res, weight, shift: bool, eps: float):
+    def forward(ctx, x, res, weight, shift: bool, eps: float, res_bias=None):
         C = dispatch.ext()
         y, s, mean, rstd = C.ln_shift_res_fwd(x, res, weight, bool(shift),
                                               float(eps))
         ctx.save_for_backward(s, weight, mean, rstd)
         ctx.shift = bool(shift)
+        ctx.bias_dtype = None if res_bias is None else res_bias.dtype
         ctx.set_materialize_grads(False)
         return y, s
 
@@ -71,20 +117,32 @@ class _LnShiftResFn(torch.autograd.Function):
         s, weight, mean, rstd = ctx.saved_tensors
         C = dispatch.ext()
         ds = ds.contiguous() if ds is not None else None
+        db = _bias_grad_buffer(ctx.bias_dtype, s.shape[-1], s.device)
         dx, dweight = C.ln_shift_res_bwd(dy.contiguous(), ds, s, weight,
-                                         mean, rstd, ctx.shift)
-        return dx, dx, dweight, None, None
+                                         mean, rstd, ctx.shift, db)
+        if db is not None:
+            db = db.to(ctx.bias_dtype)
+        return dx, dx, dweight, None, None, db
 
 
 def ln_shift_res(x: torch.Tensor, res, weight: torch.Tensor,
-                 shift: bool = True, eps: float = 1e-5):
+                 shift: bool = True, eps: float = 1e-5, res_bias=None):
     """Residual add + LN + shift in one pass: returns (y, s) with
     s = x + res (the updated residual stream) and y = ln_shift(s).
-    ``res=None`` degenerates to plain ln_shift with s = x."""
-    if dispatch.use_hip(x, "ln"):
+    ``res=None`` degenerates to plain ln_shift with s = x.
+
+    ``res_bias``: the bias parameter of the linear that produced ``res``,
+    given exactly when ``fused_dbias`` said so for that linear (which then ran
+    with the bias detached); its gradient comes out of this op's backward."""
+    hip = dispatch.use_hip(x, "ln")
+    if res_bias is not None and (res is None or not hip):
+        raise RuntimeError("ln_shift_res: res_bias needs the HIP kernel and a "
+                           "res to deliver its gradient (see fused_dbias)")
+    if hip:
         if res is None:
             return _LnShiftFn.apply(x, weight, shift, eps), x
-        return _LnShiftResFn.apply(x, res.contiguous(), weight, shift, eps)
+        return _LnShiftResFn.apply(x, res.contiguous(), weight, shift, eps,
+                                   res_bias)
     s = x if res is None else x + res
     return reference.ln_shift(s, weight, shift, eps), s
 
@@ -149,24 +207,42 @@ def local_attention(qkv: torch.Tensor, sin: torch.Tensor, cos: torch.Tensor,
 # ---------------------------------------------------------------------------
 
 class _GluGeluFn(torch.autograd.Function):
+    """``bias`` (optional) is the bias of the linear that produced ``h``,
+    unused in forward: dh is that linear's output gradient, so the backward
+    kernel also sums it per column and the sum is returned as the bias's
+    gradient (see ``fused_dbias``)."""
+
     @staticmethod
-    def forward(ctx, h):
+    def forward(ctx, h, bias=None):
         C = dispatch.ext()
         y = C.glu_fwd(h)
         ctx.save_for_backward(h)
+        ctx.bias_dtype = None if bias is None else bias.dtype
         return y
 
     @staticmethod
     def backward(ctx, dy):
         (h,) = ctx.saved_tensors
         C = dispatch.ext()
-        return C.glu_bwd(dy.contiguous(), h)
+        db = _bias_grad_buffer(ctx.bias_dtype, h.shape[-1], h.device)
+        dh = C.glu_bwd(dy.contiguous(), h, db)
+        if db is not None:
+            db = db.to(ctx.bias_dtype)
+        return dh, db
 
 
-def glu_gelu(h: torch.Tensor) -> torch.Tensor:
-    """x, gate = split(h, 2); x * gelu(gate)  (reference: progen.py:139-141)."""
-    if dispatch.use_hip(h, "glu"):
-        return _GluGeluFn.apply(h)
+def glu_gelu(h: torch.Tensor, bias=None) -> torch.Tensor:
+    """x, gate = split(h, 2); x * gelu(gate)  (reference: progen.py:139-141).
+
+    ``bias``: the bias parameter of the linear that produced ``h``, given
+    exactly when ``fused_dbias`` said so for that linear (which then ran with
+    the bias detached); its gradient comes out of this op's backward."""
+    hip = dispatch.use_hip(h, "glu")
+    if bias is not None and not hip:
+        raise RuntimeError("glu_gelu: bias needs the HIP kernel to deliver "
+                           "its gradient (see fused_dbias)")
+    if hip:
+        return _GluGeluFn.apply(h, bias)
     return reference.glu_gelu(h)
 
 

@@ -76,11 +76,19 @@ std::vector<at::Tensor> ln_shift_res_fwd(const at::Tensor& x,
 // summed stream ``s_in`` of the residual-fused variant); ``ds`` (optional)
 // is the gradient flowing into s from its later uses. With the fused
 // variant the returned dx is the gradient of BOTH addends (d(x + res) fans
-// out identically).
+// out identically). With ``db`` (fp32, (D,)) the kernel of bias_grad.hip runs
+// instead, which also sums the dx it stores per column, and ``db`` is
+// overwritten with those sums: the bias gradient of the linear that produced
+// the res addend. dx and dw are the same bits either way. That kernel keeps
+// two fp32 column accumulators in dynamic LDS, 8 * D + 32 bytes against
+// 4 * D + 32, so within the 64 KB a launch gets by default it serves
+// D <= 8176 where the call without ``db`` serves D <= 16368; a wider row is a
+// rejected launch, which LAUNCH raises.
 static std::vector<at::Tensor> ln_shift_bwd_impl(
     const char* op, const at::Tensor& dy, const c10::optional<at::Tensor>& ds,
     Arg xa, const at::Tensor& g, const at::Tensor& mean,
-    const at::Tensor& rstd, bool shift) {
+    const at::Tensor& rstd, bool shift,
+    const c10::optional<at::Tensor>& db) {
   const at::Tensor& x = xa.t;
   const bool bf = dtype_bf16_or_fp32(op, xa);
   dtype_same(op, ARG(dy), xa);
@@ -88,6 +96,7 @@ static std::vector<at::Tensor> ln_shift_bwd_impl(
   if (ds) dtype_same(op, Arg{"ds", *ds}, xa);
   dtype_is(op, ARG(mean), at::kFloat);
   dtype_is(op, ARG(rstd), at::kFloat);
+  if (db) dtype_is(op, Arg{"db", *db}, at::kFloat);
   contiguous_rank(op, xa, 3);
   const int64_t B = x.size(0), N = x.size(1), D = x.size(2);
   contiguous_shape(op, ARG(dy), x.sizes());
@@ -95,21 +104,37 @@ static std::vector<at::Tensor> ln_shift_bwd_impl(
   contiguous_numel(op, ARG(g), D);
   contiguous_numel(op, ARG(mean), B * N);
   contiguous_numel(op, ARG(rstd), B * N);
+  if (db) contiguous_shape(op, Arg{"db", *db}, {D});
   multiple_of(op, "D", D, 16);
   const int Di = extent_int(op, "D", D), Ni = extent_int(op, "N", N);
   const int R = extent_int(op, "B*N", B * N);
   same_gpu(op, {xa, ARG(dy), ARG(g), ARG(mean), ARG(rstd)});
   if (ds) same_gpu(op, {xa, Arg{"ds", *ds}});
+  if (db) same_gpu(op, {xa, Arg{"db", *db}});
 
   DeviceScope dev(x);
   const int nblocks = std::min(R, 1024);  // >=4 blocks/CU for latency hiding
   auto dx = at::empty_like(x);
   auto dw_part = at::empty({nblocks, D}, x.options().dtype(at::kFloat));
-  LAUNCH(op, ln_shift_bwd_launch(
-                 dy.data_ptr(), ds ? ds->data_ptr() : nullptr, x.data_ptr(),
-                 g.data_ptr(), mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                 dx.data_ptr(), dw_part.data_ptr<float>(), nblocks, R, Ni, Di,
-                 shift, bf, dev.stream));
+  if (db) {
+    // one more partial row per block, summed like dw's: in a fixed order
+    auto db_part = at::empty_like(dw_part);
+    LAUNCH(op, ln_shift_bwd_db_launch(
+                   dy.data_ptr(), ds ? ds->data_ptr() : nullptr, x.data_ptr(),
+                   g.data_ptr(), mean.data_ptr<float>(),
+                   rstd.data_ptr<float>(), dx.data_ptr(),
+                   dw_part.data_ptr<float>(), db_part.data_ptr<float>(),
+                   nblocks, R, Ni, Di, shift, bf, dev.stream));
+    at::Tensor db_out = *db;
+    at::sum_out(db_out, db_part, {0});
+  } else {
+    LAUNCH(op, ln_shift_bwd_launch(
+                   dy.data_ptr(), ds ? ds->data_ptr() : nullptr, x.data_ptr(),
+                   g.data_ptr(), mean.data_ptr<float>(),
+                   rstd.data_ptr<float>(), dx.data_ptr(),
+                   dw_part.data_ptr<float>(), nblocks, R, Ni, Di, shift, bf,
+                   dev.stream));
+  }
   auto dw = dw_part.sum(0).to(x.scalar_type());
   return {dx, dw};
 }
@@ -119,7 +144,7 @@ std::vector<at::Tensor> ln_shift_bwd(const at::Tensor& dy, const at::Tensor& x,
                                      const at::Tensor& mean,
                                      const at::Tensor& rstd, bool shift) {
   return ln_shift_bwd_impl("ln_shift_bwd", dy, c10::nullopt, ARG(x), g, mean,
-                           rstd, shift);
+                           rstd, shift, c10::nullopt);
 }
 
 std::vector<at::Tensor> ln_shift_res_bwd(const at::Tensor& dy,
@@ -127,9 +152,10 @@ std::vector<at::Tensor> ln_shift_res_bwd(const at::Tensor& dy,
                                          const at::Tensor& s_in,
                                          const at::Tensor& g,
                                          const at::Tensor& mean,
-                                         const at::Tensor& rstd, bool shift) {
+                                         const at::Tensor& rstd, bool shift,
+                                         const c10::optional<at::Tensor>& db) {
   return ln_shift_bwd_impl("ln_shift_res_bwd", dy, ds, ARG(s_in), g, mean,
-                           rstd, shift);
+                           rstd, shift, db);
 }
 
 // ---------------------------------------------------------------------------
@@ -156,25 +182,44 @@ at::Tensor glu_fwd(const at::Tensor& h) {
   return y;
 }
 
-at::Tensor glu_bwd(const at::Tensor& dy, const at::Tensor& h) {
+// With ``db`` (fp32, (2H,)) the kernel of bias_grad.hip runs instead, which
+// also sums the dh it stores per column, and ``db`` is overwritten with those
+// sums: the bias gradient of the linear that produced h. dh is the same bits
+// either way.
+at::Tensor glu_bwd(const at::Tensor& dy, const at::Tensor& h,
+                   const c10::optional<at::Tensor>& db) {
   const char* op = "glu_bwd";
   const bool bf = dtype_bf16_or_fp32(op, ARG(h));
   dtype_same(op, ARG(dy), ARG(h));
+  if (db) dtype_is(op, Arg{"db", *db}, at::kFloat);
   CHK(h.dim() >= 1, op, "h", h.dim(), "must have at least 1 dim");
   contiguous(op, ARG(h));
   const int64_t H2 = h.size(-1), rows = leading_rows(h);
   auto dy_sizes = h.sizes().vec();
   dy_sizes.back() = H2 / 2;
   contiguous_shape(op, ARG(dy), dy_sizes);
+  if (db) contiguous_shape(op, Arg{"db", *db}, {H2});
   multiple_of(op, "H2", H2, 16);
   const int H = extent_int(op, "H2", H2) / 2;
   extent(op, "rows", rows, INT64_MAX);
   same_gpu(op, {ARG(h), ARG(dy)});
+  if (db) same_gpu(op, {ARG(h), Arg{"db", *db}});
 
   DeviceScope dev(h);
   auto dh = at::empty_like(h);
-  LAUNCH(op, glu_bwd_launch(dy.data_ptr(), h.data_ptr(), dh.data_ptr(), rows,
-                            H, bf, dev.stream));
+  if (db) {
+    // one fp32 partial row per row stripe, summed in a fixed order
+    const int stripes = glu_bwd_db_stripes(rows, H, bf);
+    auto part = at::empty({stripes, H2}, h.options().dtype(at::kFloat));
+    LAUNCH(op, glu_bwd_db_launch(dy.data_ptr(), h.data_ptr(), dh.data_ptr(),
+                                 part.data_ptr<float>(), stripes, rows, H, bf,
+                                 dev.stream));
+    at::Tensor db_out = *db;
+    at::sum_out(db_out, part, {0});
+  } else {
+    LAUNCH(op, glu_bwd_launch(dy.data_ptr(), h.data_ptr(), dh.data_ptr(), rows,
+                              H, bf, dev.stream));
+  }
   return dh;
 }
 
@@ -694,9 +739,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ln_shift_res_fwd", &ln_shift_res_fwd,
         "residual-add-fused LN+shift forward");
   m.def("ln_shift_res_bwd", &ln_shift_res_bwd,
-        "residual-add-fused LN+shift backward");
+        "residual-add-fused LN+shift backward; db: also the column sums of dx",
+        py::arg("dy"), py::arg("ds"), py::arg("s_in"), py::arg("g"),
+        py::arg("mean"), py::arg("rstd"), py::arg("shift"),
+        py::arg("db") = py::none());
   m.def("glu_fwd", &glu_fwd, "GLU-GELU forward");
-  m.def("glu_bwd", &glu_bwd, "GLU-GELU backward");
+  m.def("glu_bwd", &glu_bwd,
+        "GLU-GELU backward; db: also the column sums of dh", py::arg("dy"),
+        py::arg("h"), py::arg("db") = py::none());
   m.def("gelu_fwd", &gelu_fwd, "GELU forward");
   m.def("gelu_bwd", &gelu_bwd, "GELU backward");
   m.def("ce_fwd", &ce_fwd, "fused CE forward (nll, lse)");

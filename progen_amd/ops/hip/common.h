@@ -188,6 +188,18 @@ __device__ __forceinline__ void vset(vec16_t<BF>& v, int j, float x) {
   else v[j] = x;
 }
 
+// A vector a kernel has just stored, made opaque to the compiler before its
+// elements are read back into a sum OF THE STORED VALUES (bias_grad.hip). Left
+// to itself the compiler folds the product behind an fp32 element into the
+// running sum as an fma, so that the sum is not of what was stored, and, with
+// the elements' second use in sight, contracts and pairs the arithmetic before
+// the store differently from the kernel without the sum: glu_bwd's fp32 dh
+// differed in the last bit between the two.
+template <typename VEC>
+__device__ __forceinline__ void opaque_vec(VEC& v) {
+  asm volatile("" : "+v"(v));
+}
+
 // sum over a 256-thread block, result in every thread. ``red`` holds 4
 // floats of LDS; consecutive calls must use different arrays.
 __device__ __forceinline__ float block256_sum(float v, float* red) {

@@ -5,8 +5,7 @@
 // and trip, grid-stride.
 
 #include "common.h"
-
-#define GLU_BLOCK 256
+#include "glu_bwd_body.h"  // GLU_BLOCK, glu_bwd_row
 
 // 2-D grid (columns x row-stripes): the flat-index form cost two
 // 64-bit integer divisions per iteration — a long VALU sequence on a
@@ -41,20 +40,8 @@ __global__ __launch_bounds__(GLU_BLOCK) void glu_bwd_kernel(
   const int i = blockIdx.x * GLU_BLOCK + (int)threadIdx.x;
   if (i >= Hv) return;
   for (long long row = blockIdx.y; row < rows; row += gridDim.y) {
-    const VEC va = h[row * 2 * Hv + i];
-    const VEC vg = h[row * 2 * Hv + Hv + i];
-    const VEC vdy = dy[row * Hv + i];
     VEC da, dg;
-#pragma unroll
-    for (int j = 0; j < vec16<BF>::N; ++j) {
-      const float d = vget<BF>(vdy, j);
-      float gv, gg;
-      gelu_tanh_both(vget<BF>(vg, j), &gv, &gg);
-      vset<BF>(da, j, d * gv);
-      vset<BF>(dg, j, d * vget<BF>(va, j) * gg);
-    }
-    dh[row * 2 * Hv + i] = da;
-    dh[row * 2 * Hv + Hv + i] = dg;
+    glu_bwd_row<BF>(dy, h, dh, row, Hv, i, da, dg);
   }
 }
 

@@ -26,6 +26,19 @@ hipError_t gelu_bwd_launch(const void* dy, const void* h, void* dh,
                            long long total_elems, bool is_bf16,
                            hipStream_t stream);
 
+// bias_grad.hip: the two backward kernels above that also write per-block
+// column sums of what they store (part: [stripes, 2H]; db_part: [nblocks, D])
+int glu_bwd_db_stripes(long long rows, int H, bool is_bf16);
+hipError_t glu_bwd_db_launch(const void* dy, const void* h, void* dh,
+                             float* part, int stripes, long long rows, int H,
+                             bool is_bf16, hipStream_t stream);
+hipError_t ln_shift_bwd_db_launch(const void* dy, const void* ds,
+                                  const void* x, const void* g,
+                                  const float* mean, const float* rstd,
+                                  void* dx, float* dw_part, float* db_part,
+                                  int nblocks, int R, int N, int D, bool shift,
+                                  bool is_bf16, hipStream_t stream);
+
 hipError_t ce_fwd_launch(const void* logits, const long long* targets,
                          float* nll, float* lse, long long R, int V,
                          bool is_bf16, hipStream_t stream);

@@ -20,12 +20,14 @@ from torch.utils.cpp_extension import BuildExtension, CUDAExtension  # noqa: E40
 # is pinned by its contract test (see EXTENSIONS in progen_amd/ops/dispatch.py,
 # which lists the same names and says what adding a module takes). The bodies
 # of the decode kernels are the decode_*_body.h headers, shared by the scalar
-# kernels and decode_slots.hip.
+# kernels and decode_slots.hip; glu_bwd_body.h and ln_shift_bwd_body.h are
+# shared by glu.hip / ln_shift.hip and bias_grad.hip.
 EXTENSIONS = {
     "progen_amd._C": [
         "progen_amd/ops/hip/bindings.cpp",
         "progen_amd/ops/hip/ln_shift.hip",
         "progen_amd/ops/hip/glu.hip",
+        "progen_amd/ops/hip/bias_grad.hip",
         "progen_amd/ops/hip/cross_entropy.hip",
         "progen_amd/ops/hip/adamw.hip",
         "progen_amd/ops/hip/rope_qkv.hip",
