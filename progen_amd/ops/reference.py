@@ -365,7 +365,11 @@ def decode_attention(
     s = torch.einsum("bhd,bhnd->bhn", q, keys) * (dh ** -0.5)
     s = s.masked_fill(~(live | halo).view(1, 1, -1), -1e30)
     s = s - s.amax(dim=-1, keepdim=True)
-    a = s.float().softmax(dim=-1).to(qkv.dtype)
+    # softmax in fp32 for the 16-bit dtypes; fp32 and fp64 keep their own
+    if s.dtype in (torch.bfloat16, torch.float16):
+        a = s.float().softmax(dim=-1).to(qkv.dtype)
+    else:
+        a = s.softmax(dim=-1)
     return torch.einsum("bhn,bhnd->bhd", a, vals).reshape(B, H * dh)
 
 

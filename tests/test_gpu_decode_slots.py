@@ -53,8 +53,11 @@ def dev_pos(pos):
 
 # ---- dec_attn_slots ---------------------------------------------------------
 
+# the last two: short bands, where some of the 32 lane groups or whole waves
+# have no row (tests/decode_oracle.py)
 ATTN = [(64, 256, [0, 63, 64, 200]), (64, 256, [-1, 127, 128, 255]),
-        (256, 512, [255, 256, 511, -1])]
+        (256, 512, [255, 256, 511, -1]), (64, 256, [1, 7, 8, 33]),
+        (64, 256, [9, 31, 32, -1])]
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["bf16", "fp32"])
