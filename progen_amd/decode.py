@@ -400,6 +400,50 @@ def prefill_supported(model: ProGenBase, P: int, device) -> bool:
         and P >= PREFILL_MIN_TOKENS
 
 
+def _rotary_fp32(model: ProGenBase):
+    """The model's rotary tables as the kernels read them, fp32."""
+    if model.rotary_sin.dtype != torch.float32:
+        sin, cos = R.fixed_pos_embedding(model.cfg.seq_len,
+                                         model.cfg.dim_head,
+                                         device=model.rotary_sin.device)
+        model.rotary_sin, model.rotary_cos = sin, cos
+    return model.rotary_sin, model.rotary_cos
+
+
+def _prefill_layers(model: ProGenBase, h: torch.Tensor, cache: DecodeCache,
+                    P: int, admit: Optional[torch.Tensor], halo):
+    """The layer loop of ``prefill`` and ``prefill_rows`` over the embedded
+    (B, Np, dim) rows ``h``: ``ProGenBase.forward``'s, with the cache writes
+    of ``OF.prefill_attention`` / ``OF.prefill_sgu`` (rows < P, and where
+    ``admit`` says when given) and ``halo(stream, weight, prev)`` storing the
+    token-shift halo of each branch. Returns the residual stream and the last
+    branch output, not yet added."""
+    sin, cos = _rotary_fp32(model)
+    r = None
+    for li, (attn, ff) in enumerate(model.layers):
+        y, h = OF.ln_shift_res(h, r, attn.norm_weight,
+                               shift=attn.shift_tokens)
+        halo(h, attn.norm_weight, cache.attn_prev[li])
+        qkv = F.linear(y, attn.to_qkv.weight)
+        out = OF.prefill_attention(qkv, sin, cos, attn.heads,
+                                   attn.window_size, cache.k[li],
+                                   cache.v[li], P, admit=admit)
+        a = F.linear(out, attn.to_out.weight, attn.to_out.bias)
+
+        y, h = OF.ln_shift_res(h, a, ff.norm_weight, shift=ff.shift_tokens)
+        halo(h, ff.norm_weight, cache.ff_prev[li])
+        t = F.linear(y, ff.proj_in.weight, ff.proj_in.bias)
+        t = OF.glu_gelu(t) if ff.glu else OF.gelu(t)
+        if ff.sgu is not None:
+            sgu = ff.sgu
+            t = OF.prefill_sgu(t, sgu.norm_weight, sgu.spatial_weights,
+                               sgu.spatial_biases, cache.gate_hist[li], P,
+                               admit=admit)
+            t = F.linear(t, sgu.proj_out.weight, sgu.proj_out.bias)
+        r = F.linear(t, ff.proj_out.weight, ff.proj_out.bias)
+    return h, r
+
+
 @torch.no_grad()
 def prefill(model: ProGenBase, tokens: torch.Tensor, cache: DecodeCache,
             pos_dev: Optional[torch.Tensor] = None,
@@ -441,11 +485,6 @@ def prefill(model: ProGenBase, tokens: torch.Tensor, cache: DecodeCache,
     if Np > cfg.seq_len:
         raise IndexError(f"prefill of {P} tokens ({Np} padded) past seq_len "
                          f"({cfg.seq_len})")
-    if model.rotary_sin.dtype != torch.float32:
-        sin, cos = R.fixed_pos_embedding(cfg.seq_len, cfg.dim_head,
-                                         device=model.rotary_sin.device)
-        model.rotary_sin, model.rotary_cos = sin, cos
-    sin, cos = model.rotary_sin, model.rotary_cos
     last = P - 1
 
     def halo(s, weight, prev):
@@ -454,27 +493,7 @@ def prefill(model: ProGenBase, tokens: torch.Tensor, cache: DecodeCache,
                                   shift=False)
 
     h = model.embed(F.pad(tokens.long(), (0, Np - P)).to(dev))  # (B, Np, dim)
-    r = None
-    for li, (attn, ff) in enumerate(model.layers):
-        y, h = OF.ln_shift_res(h, r, attn.norm_weight,
-                               shift=attn.shift_tokens)
-        halo(h, attn.norm_weight, cache.attn_prev[li])
-        qkv = F.linear(y, attn.to_qkv.weight)
-        out = OF.prefill_attention(qkv, sin, cos, attn.heads,
-                                   attn.window_size, cache.k[li],
-                                   cache.v[li], P)
-        a = F.linear(out, attn.to_out.weight, attn.to_out.bias)
-
-        y, h = OF.ln_shift_res(h, a, ff.norm_weight, shift=ff.shift_tokens)
-        halo(h, ff.norm_weight, cache.ff_prev[li])
-        t = F.linear(y, ff.proj_in.weight, ff.proj_in.bias)
-        t = OF.glu_gelu(t) if ff.glu else OF.gelu(t)
-        if ff.sgu is not None:
-            sgu = ff.sgu
-            t = OF.prefill_sgu(t, sgu.norm_weight, sgu.spatial_weights,
-                               sgu.spatial_biases, cache.gate_hist[li], P)
-            t = F.linear(t, sgu.proj_out.weight, sgu.proj_out.bias)
-        r = F.linear(t, ff.proj_out.weight, ff.proj_out.bias)
+    h, r = _prefill_layers(model, h, cache, P, None, halo)
 
     cache.pos = P
     if pos_dev is not None:
@@ -484,6 +503,37 @@ def prefill(model: ProGenBase, tokens: torch.Tensor, cache: DecodeCache,
     y = OF.decode_ln_shift(h[:, last].contiguous(), r[:, last].contiguous(),
                            model.final_norm_weight, None, shift=False)
     return F.linear(y, model.to_logits.weight, model.to_logits.bias)
+
+
+@torch.no_grad()
+def prefill_rows(model: ProGenBase, tokens: torch.Tensor, cache: DecodeCache,
+                 admit: torch.Tensor, src: torch.Tensor,
+                 live: torch.Tensor) -> None:
+    """``prefill`` for the slot engine: ONE forward over the (R, Np) device
+    ``tokens`` that fills, for every batch row r with
+    ``admit[r] = [slot, rows]`` and 0 <= slot < S, rows [0, rows) of row
+    ``slot`` of the S-row ``cache``, and nothing for any other r. Everything
+    it depends on is read from device memory, so a graph can capture it:
+    no host value but the shapes, no fill and no logits.
+
+    ``tokens``: int64, Np a length the full-sequence ops take
+    (``_prefill_len``), id 0 past each row's prime. ``admit``: (R, 2) int64.
+    ``src`` and ``live``, (S,) int64, place the token-shift halos: slot b
+    takes the LN of flat row ``src[b]`` (r * Np + rows - 1 for an admitted
+    slot, 0 otherwise) of the (R * Np, dim) stream where ``live[b] == 0``
+    and keeps its own where ``live[b] == -1`` — one
+    ``OF.decode_ln_shift_slots`` per branch, with ``live`` as its positions.
+    Each slot is named by at most one batch row. ``cache.pos`` is not used:
+    the engine keeps one position per slot."""
+    R_, Np = tokens.shape
+    D = model.cfg.dim
+
+    def halo(s, weight, prev):
+        OF.decode_ln_shift_slots(s.reshape(R_ * Np, D).index_select(0, src),
+                                 None, weight, prev, live, shift=False)
+
+    h = model.embed(tokens)                             # (R, Np, dim)
+    _prefill_layers(model, h, cache, Np, admit, halo)
 
 
 def _prefill_if_supported(model: ProGenBase, tokens: torch.Tensor,

@@ -25,13 +25,31 @@ Only copies between replays (profiles/r01_graph_interleave_bug.md): admission
 is five host-to-device copies into the slot's contiguous row views, ``pos``
 last, and polling is a device-to-host copy of ``pos`` and of the finished
 ``seq`` rows. No fill, index or arithmetic kernel ever runs on the engine's
-tensors outside the step; the eager engine runs the same code. There is no
-prefill at admission for the same reason: a prime is teacher-forced through
-the step (``len``), sharing those steps with the other slots' generation.
+tensors outside the step and the prefill graphs below; the eager engine runs
+the same code. By default a prime is teacher-forced through the step
+(``len``), sharing those steps with the other slots' generation.
+
+``prefill=True`` fills a prime's cache rows at admission instead, with one
+forward over the prime (``decode.prefill_rows``), so that the first sampled
+token is one step away instead of one step per prime token. Under the
+copies-only rule that forward is a graph of its own, one per bucket of prime
+lengths (the multiples of ``decode._prefill_len``'s unit up to seq_len) over
+static (prefill_rows, Np) token buffers, all captured in ``_build`` before
+anything is replayed. The slot and the row count of each batch row reach the
+kernels through device memory (``admit``, ops/hip/prefill_admit.hip), as do
+the places of the token-shift halos (``src``, ``live``). An admission is then
+four host-to-device copies, one replay, and the five copies of a plain
+admission with the slot entering at the prime's last position: a prime of P
+tokens is prefilled for positions [0, P-1) and the shared step samples the
+first new token from prime[P-1], as ``sample_cached_batch(prefill=True)``
+does. A prime shorter than ``prefill_min_tokens`` + 1, or with two pad
+tokens (it retires inside its prime), is teacher-forced as without the flag.
 
 A slot's caches are never cleared. A request starts at position 0, where
 the token shift reads zeros, and the attention band and the SGU prefix only
-reach rows the request wrote itself.
+reach rows the request wrote itself; a prefilled request wrote rows
+[0, P-1) and its halos, and a step writes its row before any step reads it,
+so what rows >= P-1 still hold of an earlier request is never read.
 
 Threads: ``submit`` is thread-safe and never blocks on the device. Every
 device call — allocation, capture, copies, steps — is made by ONE thread:
@@ -48,9 +66,21 @@ from typing import List, Optional
 
 import torch
 
+from . import decode
 from .decode import DecodeCache, forward_step_slots
 from .models.progen import ProGenBase
 from .ops import functional as OF
+
+
+# fewest prime positions (prime length - 1) that ``SlotEngine(prefill=True)``
+# prefills at admission. NOT yet measured through the engine
+# (profiles/engine_prefill.md lists the measurement that sets it: the
+# shortest prime at which the time to the first token wins by more than the
+# spread at 8 slots and the short-prime workload's wall time is not worse
+# than flag-off by more than its spread). Until then it is
+# ``decode.PREFILL_MIN_TOKENS``'s value, the crossover of one eager prefill
+# against the captured step at batch 1 and 8 (profiles/decode_prefill.md).
+PREFILL_MIN_TOKENS = 8
 
 
 class Ticket:
@@ -103,6 +133,8 @@ class _Row:
         # positions 0 .. limit - 2 are stepped; a one-token request still
         # takes the step in which the sampler retires it
         self.steps_left = max(int(ctl_row[0, 1]) - 1, 1)
+        self.prime_len = int(ctl_row[0, 0])
+        self.prime_pads = int((seq_row[0, :self.prime_len] == 0).sum())
 
 
 class SlotEngine:
@@ -111,16 +143,33 @@ class SlotEngine:
     run its projections on the decode linear kernel. ``check_every``: steps
     between two looks at the positions; results do not depend on it.
 
+    ``prefill``: fill a prime's cache rows with one forward at admission
+    (module docstring) instead of teacher-forcing it; ``prefill_rows``: primes
+    one such forward takes; ``prefill_min_tokens``: the fewest positions
+    worth a forward (None: ``PREFILL_MIN_TOKENS``). The tokens are those of
+    the engine without it up to the rounding of a full forward against the
+    steps. ValueError where ``decode.prefill_supported`` refuses the model at
+    every length (fp32 on a GPU).
+
     On a GPU the model must be what the slot kernels serve — bf16 or fp32,
     dim_head 64, a vocabulary of 2..1024, windows and SGU widths that are
     multiples of 64 — else ValueError: the engine never falls back."""
 
     def __init__(self, model: ProGenBase, slots: int, *, graph: bool = False,
-                 fused_linear: bool = False, check_every: int = 16):
+                 fused_linear: bool = False, check_every: int = 16,
+                 prefill: bool = False, prefill_rows: int = 1,
+                 prefill_min_tokens: Optional[int] = None):
         if slots < 1:
             raise ValueError(f"slots must be >= 1, got {slots}")
         if check_every < 1:
             raise ValueError(f"check_every must be >= 1, got {check_every}")
+        if prefill_rows < 1:
+            raise ValueError(f"prefill_rows must be >= 1, got {prefill_rows}")
+        if prefill_min_tokens is None:
+            prefill_min_tokens = PREFILL_MIN_TOKENS
+        if prefill_min_tokens < 1:
+            raise ValueError("prefill_min_tokens must be >= 1, got "
+                             f"{prefill_min_tokens}")
         self.model = model
         self.cfg = model.cfg
         self.slots = int(slots)
@@ -131,7 +180,22 @@ class SlotEngine:
         self.graph = bool(graph) and self.device.type == "cuda"
         if self.device.type == "cuda":
             self._check_supported(p.dtype)
-
+        self.prefill = bool(prefill)
+        self.prefill_rows = int(prefill_rows)
+        self.prefill_min_tokens = int(prefill_min_tokens)
+        # padded lengths of the prefill forwards, ascending
+        self._buckets: List[int] = []
+        if self.prefill:
+            unit = decode._prefill_len(model, 1, self.device)
+            self._buckets = list(range(unit, self.cfg.seq_len + 1, unit))
+            if not any(decode.prefill_supported(model, n, self.device)
+                       for n in self._buckets):
+                raise ValueError(
+                    "SlotEngine: prefill=True, but decode.prefill_supported "
+                    f"refuses this model on {self.device} at every length "
+                    "(on a GPU: bf16, dim_head 64, window and SGU width "
+                    f"multiples of 64, {unit} padded rows within seq_len "
+                    f"{self.cfg.seq_len})")
         self._lock = threading.Condition()
         self._queue = collections.deque()            # _Row, FIFO
         self._active: List[Optional[_Row]] = [None] * self.slots
@@ -145,6 +209,9 @@ class SlotEngine:
         # frees it)
         self.steps = 0
         self.occupied_slot_steps = 0
+        # prefill forwards run, and prime positions they covered
+        self.prefills = 0
+        self.prefilled_positions = 0
 
     def _check_supported(self, dtype) -> None:
         cfg = self.cfg
@@ -330,21 +397,42 @@ class SlotEngine:
         self.pads = torch.zeros(S, dtype=torch.long).to(dev, copy=True)
         self.ctl = torch.zeros(S, len(OF.SLOT_CTL),
                                dtype=torch.long).to(dev, copy=True)
+        # prefill at admission: static inputs of the forwards, one token
+        # buffer per bucket; no batch row admits anything yet
+        R = self.prefill_rows
+        self._pf_tokens = {
+            n: torch.zeros(R, n, dtype=torch.long).to(dev, copy=True)
+            for n in self._buckets}
+        self._pf_admit = torch.tensor([[-1, 0]] * R,
+                                      dtype=torch.long).to(dev, copy=True)
+        self._pf_src = torch.zeros(S, dtype=torch.long).to(dev, copy=True)
+        self._pf_live = torch.full((S,), -1,
+                                   dtype=torch.long).to(dev, copy=True)
         self._graph = None
+        self._pf_graphs = {}
         if not self.graph:
             return
-        # every slot is idle: warm-up and capture change no cache, sequence
-        # or position, so there is nothing to snapshot and restore
+        # every slot is idle and no batch row admits: warm-up and capture
+        # change no cache, halo, sequence or position, so there is nothing to
+        # snapshot and restore. Every graph is captured before the first
+        # replay of any.
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(2):
                 self._step()
+                for n in self._buckets:
+                    self._prefill_forward(n)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self._graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self._graph):
             self._step()
+        for n in self._buckets:
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._prefill_forward(n)
+            self._pf_graphs[n] = g
         torch.cuda.synchronize()
 
     def _step(self) -> None:
@@ -353,16 +441,61 @@ class SlotEngine:
         OF.decode_sample_slots(logits, self.pos, self.token, self.seq,
                                self.pads, self.ctl)
 
-    def _admit(self, b: int, row: _Row) -> None:
-        """Start ``row`` in slot ``b``: copies into the slot's row views,
-        the position last."""
-        first = row.seq_row[:, 0].contiguous()               # (1,)
+    def _prefill_forward(self, n: int) -> None:
+        decode.prefill_rows(self.model, self._pf_tokens[n], self.cache,
+                            self._pf_admit, self._pf_src, self._pf_live)
+
+    def _admit(self, b: int, row: _Row, at: int = 0) -> None:
+        """Start ``row`` in slot ``b`` at position ``at`` (0, or past the
+        positions a prefill covered): copies into the slot's row views, the
+        position last."""
+        token = row.seq_row[:, at].contiguous()              # (1,)
         self.seq[b:b + 1].copy_(row.seq_row)
-        self.token[b:b + 1].copy_(first)
-        # position 0 is written at entry and counts if it is a pad
-        self.pads[b:b + 1].copy_((first == 0).long())
+        self.token[b:b + 1].copy_(token)
+        # positions 0 .. at are written at entry and count where they are pads
+        self.pads[b:b + 1].copy_(
+            (row.seq_row[:, :at + 1] == 0).sum(dim=1))
         self.ctl[b:b + 1].copy_(row.ctl_row)
-        self.pos[b:b + 1].copy_(torch.zeros(1, dtype=torch.long))
+        self.pos[b:b + 1].copy_(torch.full((1,), at, dtype=torch.long))
+        row.steps_left -= at
+
+    def _prefill_bucket(self, row: _Row) -> Optional[int]:
+        """The padded length of the forward that prefills ``row``'s prime, or
+        None when the row is teacher-forced: prefill is off, the prime is too
+        short to be worth a forward, it retires inside its prime (two pads),
+        or no bucket holds it."""
+        n = row.prime_len - 1
+        if not self.prefill or n < self.prefill_min_tokens \
+                or row.prime_pads > 1:
+            return None
+        return next((np_ for np_ in self._buckets if np_ >= n), None)
+
+    def _admit_prefilled(self, np_: int, chunk) -> None:
+        """One prefill forward of ``np_`` padded rows for the
+        (slot, row) pairs of ``chunk``, at most ``prefill_rows`` of them, then
+        their admission at the last prime position."""
+        R, S = self.prefill_rows, self.slots
+        tokens = torch.zeros(R, np_, dtype=torch.long)
+        admit = torch.tensor([[-1, 0]] * R, dtype=torch.long)
+        src = torch.zeros(S, dtype=torch.long)
+        live = torch.full((S,), -1, dtype=torch.long)
+        for r, (b, row) in enumerate(chunk):
+            n = row.prime_len - 1
+            tokens[r, :n] = row.seq_row[0, :n]
+            admit[r, 0], admit[r, 1] = b, n
+            src[b], live[b] = r * np_ + n - 1, 0
+            self.prefilled_positions += n
+        self._pf_tokens[np_].copy_(tokens)
+        self._pf_admit.copy_(admit)
+        self._pf_src.copy_(src)
+        self._pf_live.copy_(live)
+        if self._graph is not None:
+            self._pf_graphs[np_].replay()
+        else:
+            self._prefill_forward(np_)
+        self.prefills += 1
+        for b, row in chunk:
+            self._admit(b, row, at=row.prime_len - 1)
 
     @torch.no_grad()
     def cycle(self) -> None:
@@ -383,8 +516,16 @@ class SlotEngine:
                     self._active[b] = row
                     row.ticket.slots[row.index] = b
                     admitted.append((b, row))
+        groups = {}                     # bucket -> [(slot, row)]
         for b, row in admitted:
-            self._admit(b, row)
+            np_ = self._prefill_bucket(row)
+            if np_ is None:
+                self._admit(b, row)
+            else:
+                groups.setdefault(np_, []).append((b, row))
+        for np_, group in sorted(groups.items()):
+            for i in range(0, len(group), self.prefill_rows):
+                self._admit_prefilled(np_, group[i:i + self.prefill_rows])
 
         # 2. step: as many as the longest active row can still need
         active = [r for r in self._active if r is not None]

@@ -483,11 +483,15 @@ def decode_linear(x: torch.Tensor, w: torch.Tensor, bias=None,
 # ---------------------------------------------------------------------------
 # The full-sequence attention and SGU ops over a (B, Np) prime, which also
 # leave rows [0, P) of the decode caches as P decode steps would have — see
-# decode.prefill. ``P`` is a host int; no autograd.
+# decode.prefill. ``P`` is a host int; no autograd. ``admit``, a (B, 2) int64
+# device tensor of [slot, rows] per batch row, sends batch row b's rows
+# [0, min(rows, P)) to row ``slot`` of caches of any number of rows instead,
+# and nowhere when the slot is out of range — see decode.prefill_rows.
 
 def prefill_attention(qkv: torch.Tensor, sin: torch.Tensor, cos: torch.Tensor,
                       heads: int, window_size: int, k_cache: torch.Tensor,
-                      v_cache: torch.Tensor, P: int) -> torch.Tensor:
+                      v_cache: torch.Tensor, P: int,
+                      admit=None) -> torch.Tensor:
     """``local_attention`` of qkv (B, Np, 3*H*dh) that also stores the rotated
     k and v of rows < P into the (B, H, Nc, dh) caches
     (reference.prefill_attention). ``sin``/``cos`` hold at least Np rows. On
@@ -495,17 +499,18 @@ def prefill_attention(qkv: torch.Tensor, sin: torch.Tensor, cos: torch.Tensor,
     attention is ``attn_fwd``, bf16 only."""
     if dispatch.use_hip(qkv, "prefill_kv"):
         qkv_rot = dispatch.ext_prefill().prefill_rope_kv(
-            qkv.contiguous(), sin, cos, k_cache, v_cache, int(P))
+            qkv.contiguous(), sin, cos, k_cache, v_cache, int(P), admit)
         out, _lse = dispatch.ext().attn_fwd(qkv_rot, int(heads),
                                             int(window_size))
         return out
     return reference.prefill_attention(qkv, sin, cos, heads, window_size,
-                                       k_cache, v_cache, int(P))
+                                       k_cache, v_cache, int(P), admit)
 
 
 def prefill_sgu(x: torch.Tensor, norm_weight: torch.Tensor,
                 spatial_weights: torch.Tensor, spatial_biases: torch.Tensor,
-                hist: torch.Tensor, P: int, eps: float = 1e-5) -> torch.Tensor:
+                hist: torch.Tensor, P: int, eps: float = 1e-5,
+                admit=None) -> torch.Tensor:
     """``sgu_gate`` of x (B, Np, 2*d2) that also stores the LN'd gate rows
     < P into the (B, Nc, d2) history (reference.prefill_sgu). On a GPU the
     gate LN reads its half of ``x`` in place and writes the history in the
@@ -513,7 +518,7 @@ def prefill_sgu(x: torch.Tensor, norm_weight: torch.Tensor,
     Np % 256 == 0 and d2 % 64 == 0, or the kernels raise."""
     if dispatch.use_hip(x, "prefill_gate"):
         gate_ln = dispatch.ext_prefill().prefill_gate_ln(
-            x.contiguous(), norm_weight, hist, int(P), float(eps))
+            x.contiguous(), norm_weight, hist, int(P), float(eps), admit)
         n = x.shape[1]
         xa = x[..., :x.shape[-1] // 2].contiguous()
         out, _gate_out = dispatch.ext().sgu_fwd(
@@ -521,7 +526,7 @@ def prefill_sgu(x: torch.Tensor, norm_weight: torch.Tensor,
             spatial_biases[:n])
         return out
     return reference.prefill_sgu(x, norm_weight, spatial_weights,
-                                 spatial_biases, hist, int(P), eps)
+                                 spatial_biases, hist, int(P), eps, admit)
 
 
 # ---------------------------------------------------------------------------

@@ -18,4 +18,20 @@ hipError_t prefill_gate_ln_launch(const void* x, const void* g, void* gate_ln,
                                   void* hist, int R, int Np, int Nc, int d2,
                                   int P, float eps, hipStream_t stream);
 
+// The same two with the cache row and the row count read from device memory
+// (prefill_admit.hip): admit (R, 2) int64 = [slot, rows] per batch row; the
+// caches have S rows, and batch row r writes rows [0, min(rows, P)) of cache
+// row ``slot`` when 0 <= slot < S, else nothing.
+hipError_t admit_rope_kv_launch(const void* qkv, const float* rsin,
+                                const float* rcos, void* qkv_rot,
+                                void* k_cache, void* v_cache,
+                                const long long* admit, int R, int Np, int H,
+                                int Nc, int S, int P, hipStream_t stream);
+
+// rows = R * Np.
+hipError_t admit_gate_ln_launch(const void* x, const void* g, void* gate_ln,
+                                void* hist, const long long* admit, int rows,
+                                int Np, int Nc, int d2, int S, int P, float eps,
+                                hipStream_t stream);
+
 }  // extern "C"

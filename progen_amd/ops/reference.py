@@ -422,6 +422,22 @@ def decode_linear(x: torch.Tensor, w: torch.Tensor, bias, act: str = "none"
 # One full-sequence forward over the prime leaves in the caches what the
 # decode steps of its positions would have stored. ``P`` is a host int; only
 # cache rows [0, P) are written. Everything runs in the inputs' dtype.
+#
+# With ``admit``, a (B, 2) int64 tensor of [slot, rows] per batch row, the
+# caches have any number S of rows: batch row b fills rows [0, min(rows, P))
+# of cache row ``slot`` when 0 <= slot < S, and no cache row otherwise
+# (ops/hip/prefill_admit.hip). The values are read on the host here, so like
+# the slot references these cannot be captured in a graph.
+
+def _admitted(admit: torch.Tensor, B: int, S: int, P: int):
+    """(batch row, slot, rows) of every batch row of ``admit`` that stores
+    anything."""
+    assert admit.dtype == torch.int64 and admit.shape == (B, 2), \
+        f"admit must be int64 ({B}, 2), got {admit.dtype} {tuple(admit.shape)}"
+    return [(b, slot, min(rows, P))
+            for b, (slot, rows) in enumerate(admit.tolist())
+            if 0 <= slot < S and rows > 0]
+
 
 def prefill_rope_kv(
     qkv: torch.Tensor,
@@ -430,12 +446,14 @@ def prefill_rope_kv(
     k_cache: torch.Tensor,
     v_cache: torch.Tensor,
     P: int,
+    admit: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Interleaved rotary on q, k and v of qkv (B, N, 3*H*dh) at positions
     0..N-1; the rotated k and v of rows < P are stored head-major into
-    k_cache/v_cache (B, H, Nc, dh). Returns the rotated qkv."""
+    k_cache/v_cache (B, H, Nc, dh), or as ``admit`` says into (S, H, Nc, dh).
+    Returns the rotated qkv."""
     B, N, C = qkv.shape
-    _, H, Nc, dh = k_cache.shape
+    S, H, Nc, dh = k_cache.shape
     if not 1 <= P <= min(N, Nc):
         raise ValueError(f"prefill_rope_kv: P must be in [1, {min(N, Nc)}], "
                          f"got {P}")
@@ -443,8 +461,13 @@ def prefill_rope_kv(
     s = rsin[:N].to(qkv.dtype).reshape(1, N, 1, dh)
     c = rcos[:N].to(qkv.dtype).reshape(1, N, 1, dh)
     rot = x * c + rotate_every_two(x) * s
-    k_cache[:, :, :P] = rot[:, :P, H:2 * H].transpose(1, 2)
-    v_cache[:, :, :P] = rot[:, :P, 2 * H:].transpose(1, 2)
+    if admit is None:
+        k_cache[:, :, :P] = rot[:, :P, H:2 * H].transpose(1, 2)
+        v_cache[:, :, :P] = rot[:, :P, 2 * H:].transpose(1, 2)
+    else:
+        for b, slot, n in _admitted(admit, B, S, P):
+            k_cache[slot, :, :n] = rot[b, :n, H:2 * H].transpose(0, 1)
+            v_cache[slot, :, :n] = rot[b, :n, 2 * H:].transpose(0, 1)
     return rot.reshape(B, N, C)
 
 
@@ -457,11 +480,13 @@ def prefill_attention(
     k_cache: torch.Tensor,
     v_cache: torch.Tensor,
     P: int,
+    admit: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """``local_attention`` over the whole (B, N, 3*H*dh) qkv, with the
-    rotated k/v rows < P left in the caches."""
+    rotated k/v rows < P left in the caches (``admit``: in the rows of the
+    slots it names)."""
     N = qkv.shape[1]
-    prefill_rope_kv(qkv, rsin, rcos, k_cache, v_cache, P)
+    prefill_rope_kv(qkv, rsin, rcos, k_cache, v_cache, P, admit)
     return local_attention(qkv, rsin[:N], rcos[:N], heads, window)
 
 
@@ -471,15 +496,21 @@ def prefill_gate_ln(
     hist: torch.Tensor,
     P: int,
     eps: float = 1e-5,
+    admit: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Scale-only LN of the gate half of x (B, N, 2*d2); rows < P are stored
-    into hist (B, Nc, d2). Returns the (B, N, d2) LN'd gate."""
+    into hist (B, Nc, d2), or as ``admit`` says into (S, Nc, d2). Returns the
+    (B, N, d2) LN'd gate."""
     N, Nc = x.shape[1], hist.shape[1]
     if not 1 <= P <= min(N, Nc):
         raise ValueError(f"prefill_gate_ln: P must be in [1, {min(N, Nc)}], "
                          f"got {P}")
     gate_ln = layernorm_nobias(x.chunk(2, dim=-1)[1], g, eps)
-    hist[:, :P] = gate_ln[:, :P]
+    if admit is None:
+        hist[:, :P] = gate_ln[:, :P]
+    else:
+        for b, slot, n in _admitted(admit, x.shape[0], hist.shape[0], P):
+            hist[slot, :n] = gate_ln[b, :n]
     return gate_ln
 
 
@@ -491,11 +522,13 @@ def prefill_sgu(
     hist: torch.Tensor,
     P: int,
     eps: float = 1e-5,
+    admit: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """``sgu_gate`` over the whole (B, N, 2*d2) activation, with the LN'd
-    gate rows < P left in ``hist``."""
+    gate rows < P left in ``hist`` (``admit``: in the rows of the slots it
+    names)."""
     n = x.shape[1]
-    gate_ln = prefill_gate_ln(x, g, hist, P, eps)
+    gate_ln = prefill_gate_ln(x, g, hist, P, eps, admit)
     wl = w[:n, :n].tril().to(gate_ln.dtype)
     gate = torch.einsum("bnd,mn->bmd", gate_ln, wl) + \
         bias[:n].to(gate_ln.dtype)

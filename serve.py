@@ -34,7 +34,10 @@ the lock: they go through one ``progen_amd.engine.SlotEngine``, a persistent
 decode batch of N rows in which every row serves its own request at its own
 position. Concurrent requests then share each decode step, a finished row
 frees its slot at once, and with --graph the step is captured once for the
-life of the server.
+life of the server. With --slot-prefill the engine fills a request's prime
+into its slot with one forward at admission (captured too under --graph)
+instead of feeding it through the shared step one token per step; --prefill
+belongs to the one-request-at-a-time path and stays refused with --slots.
 """
 
 import contextlib
@@ -58,13 +61,16 @@ def create_app(module: ProGenBase, cfg: ProGenConfig, *,
                device_sampling: bool = False,
                prefill: bool = False,
                slots: int = 0,
+               slot_prefill: bool = False,
                meta: Optional[dict] = None):
     """Build the FastAPI app around a ready (device-placed, eval) module.
     ``slots`` > 0 serves /generate from one started ``SlotEngine`` of that
-    many rows; the thread it starts then owns the module's device calls."""
+    many rows; the thread it starts then owns the module's device calls.
+    ``slot_prefill``: that engine prefills a request's prime at admission."""
     if fused_linear and not fused:
         raise ValueError("fused_linear=True needs fused=True")
-    _check_slots(slots, fused, device_sampling, prefill, ValueError)
+    _check_slots(slots, fused, device_sampling, prefill, ValueError,
+                 slot_prefill=slot_prefill)
     from fastapi import FastAPI, HTTPException
     from pydantic import BaseModel
 
@@ -89,13 +95,15 @@ def create_app(module: ProGenBase, cfg: ProGenConfig, *,
         "device_sampling": bool(device_sampling),
         "prefill": bool(prefill),
         "slots": int(slots),
+        "slot_prefill": bool(slot_prefill),
         **(meta or {}),
     }
     engine = None
     if slots:
         from progen_amd.engine import SlotEngine
         engine = SlotEngine(module, slots, graph=info["graph"],
-                            fused_linear=fused_linear).start()
+                            fused_linear=fused_linear,
+                            prefill=slot_prefill).start()
 
     class GenerateRequest(BaseModel):
         primes: Optional[List[str]] = None
@@ -166,12 +174,15 @@ def create_app(module: ProGenBase, cfg: ProGenConfig, *,
 
 
 def _check_slots(slots, fused, device_sampling, prefill, error,
-                 opt=str) -> None:
-    """``slots`` runs the fused step with the device sampler and has no
-    prefill at admission; anything else is a usage error. ``opt`` spells an
-    option's name for the message."""
+                 opt=str, slot_prefill=False) -> None:
+    """``slots`` runs the fused step with the device sampler, and its prefill
+    at admission is ``slot_prefill``, not the samplers' ``prefill``; anything
+    else is a usage error. ``opt`` spells an option's name for the message."""
     if slots < 0:
         raise error(f"{opt('slots')} must be >= 0")
+    if slot_prefill and not slots:
+        raise error(f"{opt('slot_prefill')} needs {opt('slots')}: it is the "
+                    "slot engine's prefill at admission")
     if not slots:
         return
     if not (fused and device_sampling):
@@ -234,12 +245,17 @@ def load_module(checkpoint_path: str):
                    "batch of this many rows, each at its own position "
                    "(needs --fused and --device-sampling; 0 = one request "
                    "at a time)")
+@click.option("--slot-prefill", "slot_prefill", default=False, is_flag=True,
+              help="with --slots: fill a request's prime into its slot with "
+                   "one forward at admission instead of one shared step per "
+                   "prime token")
 def main(checkpoint_path, host, port, graph, fused, fused_linear,
-         device_sampling, prefill, slots):
+         device_sampling, prefill, slots, slot_prefill):
     if fused_linear and not fused:
         raise click.UsageError("--fused-linear needs --fused")
     _check_slots(slots, fused, device_sampling, prefill, click.UsageError,
-                 opt=lambda name: "--" + name.replace("_", "-"))
+                 opt=lambda name: "--" + name.replace("_", "-"),
+                 slot_prefill=slot_prefill)
     load_dotenv()
     from progen_amd.tuning import enable_tuned_gemms
     enable_tuned_gemms()
@@ -248,7 +264,7 @@ def main(checkpoint_path, host, port, graph, fused, fused_linear,
     app = create_app(module, cfg, graph=graph, fused=fused,
                      fused_linear=fused_linear,
                      device_sampling=device_sampling, prefill=prefill,
-                     slots=slots, meta=meta)
+                     slots=slots, slot_prefill=slot_prefill, meta=meta)
     uvicorn.run(app, host=host, port=port, log_level="info")
 
 

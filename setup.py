@@ -20,7 +20,8 @@ from torch.utils.cpp_extension import BuildExtension, CUDAExtension  # noqa: E40
 # is pinned by its contract test (see EXTENSIONS in progen_amd/ops/dispatch.py,
 # which lists the same names and says what adding a module takes). The bodies
 # of the decode kernels are the decode_*_body.h headers, shared by the scalar
-# kernels and decode_slots.hip; glu_bwd_body.h and ln_shift_bwd_body.h are
+# kernels and decode_slots.hip; prefill_body.h is shared by prefill.hip and
+# prefill_admit.hip; glu_bwd_body.h and ln_shift_bwd_body.h are
 # shared by glu.hip / ln_shift.hip and bias_grad.hip.
 EXTENSIONS = {
     "progen_amd._C": [
@@ -58,6 +59,7 @@ EXTENSIONS = {
     "progen_amd._C_prefill": [
         "progen_amd/ops/hip/prefill_bindings.cpp",
         "progen_amd/ops/hip/prefill.hip",
+        "progen_amd/ops/hip/prefill_admit.hip",
     ],
     # the decode kernels with one position per batch row (progen_amd/engine.py)
     "progen_amd._C_decode_slots": [

@@ -28,11 +28,14 @@ single-prime requests of seeded ragged lengths, all waiting at time 0:
 through the engine with N slots, or with --slots 0 one
 ``sample_cached_batch`` per request in sequence, as serve.py runs them under
 its lock; it reports the wall time, generated tokens/s, the request latency
-percentiles and the engine's mean slot occupancy.
+percentiles and the engine's mean slot occupancy. --slot-prefill turns on the
+engine's prefill at admission (--prefill-rows, --prefill-min-tokens), and
+--prime-range LO HI draws the primes from LO..HI instead of 4..64, the drawn
+64..512 then counting the tokens generated after the prime.
 
 Usage (GPU box):  python tools/bench_decode.py [--tokens 128] [--graph] [--fused [--fused-linear]] [--batch 8] [--device-sampling] [--top-k 25]
                   python tools/bench_decode.py --prime-len 512 [--prefill] --graph --fused --fused-linear [--batch 8]
-                  python tools/bench_decode.py --slots 16 --graph --fused --fused-linear --device-sampling --top-k 25 [--requests 64]
+                  python tools/bench_decode.py --slots 16 --graph --fused --fused-linear --device-sampling --top-k 25 [--requests 64 [--slot-prefill] [--prime-range 64 512]]
 """
 
 import argparse
@@ -92,7 +95,26 @@ def parse_args(argv=None):
     ap.add_argument("--requests", type=int, default=0,
                     help="with --slots: serve this many single-prime requests "
                          "of seeded prime lengths 4..64 and lengths 64..512")
+    ap.add_argument("--slot-prefill", action="store_true",
+                    help="with --slots N >= 1: the engine prefills a prime "
+                         "at admission instead of teacher-forcing it")
+    ap.add_argument("--prefill-rows", type=int, default=1,
+                    help="with --slot-prefill: primes per prefill forward")
+    ap.add_argument("--prefill-min-tokens", type=int, default=None,
+                    help="with --slot-prefill: fewest prime positions worth "
+                         "a forward (default: the engine's)")
+    ap.add_argument("--prime-range", type=int, nargs=2, default=None,
+                    metavar=("LO", "HI"),
+                    help="with --requests: prime lengths LO..HI instead of "
+                         "4..64; the drawn 64..512 is then the number of "
+                         "tokens after the prime, cut at seq_len")
     args = ap.parse_args(argv)
+    if args.slot_prefill and not args.slots:
+        ap.error("--slot-prefill needs --slots N >= 1")
+    if args.prime_range is not None and (
+            not args.requests or
+            not 1 <= args.prime_range[0] <= args.prime_range[1]):
+        ap.error("--prime-range needs --requests and 1 <= LO <= HI")
     if args.slots is not None:
         if not (args.fused and args.device_sampling) or args.prefill \
                 or args.prime_len:
@@ -413,15 +435,24 @@ def run_slot_step(m, args):
 
 def slot_workload(args, seq_len):
     """The --requests workload: (prime, length) per request, seeded. Prime
-    lengths 4..64, lengths 64..512 and never past seq_len."""
+    lengths 4..64, lengths 64..512 and never past seq_len. With
+    --prime-range LO HI the primes have LO..HI tokens (below seq_len) and the
+    drawn 64..512 counts the tokens after the prime."""
     g = torch.Generator().manual_seed(args.seed)
+    lo, hi = args.prime_range or (4, 64)
     out = []
     for _ in range(args.requests):
-        n = int(torch.randint(4, 65, (1,), generator=g))
-        length = min(int(torch.randint(64, 513, (1,), generator=g)), seq_len)
-        length = max(length, n + 1)
+        n = min(int(torch.randint(lo, hi + 1, (1,), generator=g)), seq_len - 1)
+        length = int(torch.randint(64, 513, (1,), generator=g))
+        if args.prime_range is not None:
+            length += n
+        length = max(min(length, seq_len), n + 1)
         out.append((torch.randint(1, 256, (n,), generator=g), length))
     return out
+
+
+def lo_hi(args):
+    return "{}..{}".format(*args.prime_range)
 
 
 def run_slot_workload(m, args):
@@ -441,7 +472,10 @@ def run_slot_workload(m, args):
     if args.slots:
         engine = SlotEngine(m, args.slots, graph=args.graph,
                             fused_linear=args.fused_linear,
-                            check_every=args.check_every)
+                            check_every=args.check_every,
+                            prefill=args.slot_prefill,
+                            prefill_rows=args.prefill_rows,
+                            prefill_min_tokens=args.prefill_min_tokens)
         # the engine's one cache and capture belong to the server's start,
         # not to a request: built before the clock starts and reported apart
         # (the sequential arm pays a cache and a capture inside every request)
@@ -452,6 +486,7 @@ def run_slot_workload(m, args):
         torch.cuda.synchronize()
         build_s = time.perf_counter() - tb
         steps0, occ0 = engine.steps, engine.occupied_slot_steps
+        pf0 = engine.prefills
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         tickets = [engine.submit([p], length, top_k=top_k, seed=s)
@@ -482,6 +517,14 @@ def run_slot_workload(m, args):
         (f"+top{args.top_k}" if args.top_k else "")
     arm = f"engine, {args.slots} slots" if args.slots else \
         "one request at a time"
+    if args.slot_prefill:
+        arm += (f", prefill at admission (rows {engine.prefill_rows}, min "
+                f"{engine.prefill_min_tokens}): {engine.prefills - pf0} "
+                f"forwards, {engine.steps - steps0} steps")
+    elif args.slots:
+        arm += f", {engine.steps - steps0} steps"
+    if args.prime_range is not None:
+        arm += f"; primes {lo_hi(args)}"
     occ = "" if occupancy is None else \
         (f", mean slot occupancy {occupancy:.2f}; engine build + capture + "
          f"first request {build_s:.2f} s, not in the wall time")
